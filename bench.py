@@ -7,8 +7,17 @@ layers, lm_head + shifted masked CE, the complete backward, bucketed RCCL gradie
 (N>1), global-norm clip and fused AdamW. Per-GPU batch 8 (config 3; config 4 at N=8 = global
 64), weak scaling. Random-init weights (no checkpoints offline), synthetic data.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, then the
+JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, config, mfu, loss).
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (float32):
+the loss, and from every trainable arena a fixed, seeded sample of the updated parameters and of
+the gradients (a few MB per array). Weights, batch and sample indices are seeded, so two builds
+run with the same arguments can be compared array for array. Everything else below (the traced
+roofline pass, library ceilings, cpu_baseline, the other workloads, the exchange figures, the
+sidecar record) is measured with `--full` only.
 
 `--gpus N > 1` without a launcher env (no WORLD_SIZE) starts the N ranks itself, before this process
 touches the GPU: a child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -16,7 +25,7 @@ touches the GPU: a child `python -m torch.distributed.run --nnodes=1 --nproc-per
 /root/reference/run:59-71 `accelerate launch --num_processes`); rank 0's JSON line is forwarded
 and the child's exit code returned. A formed world that differs from --gpus is an error (exit 3).
 
-At N = 1 the default run also times the other BASELINE workloads, each in a child process started
+At N = 1 a `--full` run also times the other BASELINE workloads, each in a child process started
 before this process touches the GPU (so their memory never overlaps): config 2 (CLIP ViT-L/14-336
 encoder, bs 64), config 5 (ViT-L + Llama-2-13B, L = 1600, bs 4) and the reference's own recipe on
 config 3 (LoRA r=64 + projector / lm_head / embed, frozen base). They are reported under
@@ -66,8 +75,14 @@ def parse(argv=None):
                     help="step: the training step (default; configs 3/4/5 by --config/--batch/--text-len); "
                          "vit: BASELINE config 2, the CLIP ViT-L/14-336 encoder forward at bs=--batch (64); "
                          "decode: 7B KV-cache decode (the step-2-pre generate path) at batch --batch")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the traced roofline "
+                         "pass, library ceilings, cpu_baseline, the other workloads (N = 1), the exchange (N > 1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="training step only: write the last timed step's loss and a seeded sample of every "
+                         "trainable arena's updated parameters and gradients to DIR/<name>.npy (float32)")
     ap.add_argument("--sub-workloads", default=",".join(SUB_WORKLOADS),
-                    help="N=1 headline runs only: the other workloads timed in child processes ('' = none)")
+                    help="--full N=1 headline runs only: the other workloads timed in child processes ('' = none)")
     ap.add_argument("--no-sub", action="store_true", help="time this workload only")
     ap.add_argument("--detail-out", default=os.path.join(REPO, "gpurun_out", "bench_detail.json"),
                     help="sidecar file for the full record ('' = none); the stdout line stays compact")
@@ -105,7 +120,7 @@ def run_sub_workloads(args, names):
     for name in names:
         fd, side = tempfile.mkstemp(prefix=f"bench_{name}_", suffix=".json")
         os.close(fd)
-        cmd = [sys.executable, os.path.abspath(__file__), "--no-sub", "--no-cpu-baseline", "--detail-out", side,
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-sub", "--no-cpu-baseline", "--detail-out", side,
                "--steps", str(min(args.steps, 10)), "--warmup", str(min(args.warmup, 3)), *SUB_WORKLOADS[name]]
         t0 = time.perf_counter()
         try:
@@ -164,10 +179,11 @@ def compact_line(full: dict) -> dict:
     line = {k: full[k] for k in HEAD_KEYS if k in full}
     if isinstance(line.get("config"), dict) and "workload" in line["config"]:
         line["config"] = dict(line["config"], workload=_short(line["config"]["workload"], 220))
-    roof = full.get("roofline") or {}
-    line["roofline"] = {k: roof[k] for k in ROOF_KEYS if k in roof}
-    if "kernel" in line["roofline"]:
-        line["roofline"]["kernel"] = _short(line["roofline"]["kernel"], 260)
+    roof = full.get("roofline")
+    if roof:  # --full runs (a plain run times the headline only)
+        line["roofline"] = {k: roof[k] for k in ROOF_KEYS if k in roof}
+        if "kernel" in line["roofline"]:
+            line["roofline"]["kernel"] = _short(line["roofline"]["kernel"], 260)
     for k in ("layer_roofline", "step_roofline", "exchange"):
         if k in full:
             line[k] = full[k]
@@ -191,8 +207,12 @@ def compact_line(full: dict) -> dict:
 
 
 def emit(full: dict, args) -> None:
-    """Full record to the sidecar (if any), then the compact line as the last line of stdout."""
+    """Full record to the sidecar (if any), then the compact line as the last line of stdout.
+    A plain run's record is its line: the default sidecar is written by --full runs only (a
+    --detail-out given explicitly is always honoured)."""
     path = getattr(args, "detail_out", "")
+    if path == parse([]).detail_out and not getattr(args, "full", True):
+        path = ""
     if path:
         try:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -203,6 +223,36 @@ def emit(full: dict, args) -> None:
             print(f"bench.py: could not write {path}: {e}", file=sys.stderr)
     print(json.dumps(compact_line(full)), flush=True)
 
+
+DUMP_BLOCK = 1024  # contiguous elements per sampled block
+DUMP_SAMPLE = 512 * DUMP_BLOCK  # elements kept per dumped array (2 MiB of float32; <= 12 arrays + the loss)
+
+
+def dump_outputs(out_dir: str, loss, arenas) -> None:
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy: loss.npy [1],
+    and per trainable arena param_<arena>.npy (the parameters after the step's AdamW update) and
+    grad_<arena>.npy (the gradients the step's backward left): DUMP_SAMPLE elements in blocks of
+    DUMP_BLOCK, the block starts drawn once (sorted) from a CPU generator seeded by the arena's
+    position, or the whole arena when it is smaller. Blocks are plain slices, so arenas past
+    2^31 elements need no wide gather. The starts depend on the arena sizes only: runs with the
+    same arguments dump the same elements."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    loss = torch.as_tensor(loss).detach().float().reshape(1).cpu()
+    np.save(os.path.join(out_dir, "loss.npy"), loss.numpy())
+    for i, ar in enumerate(a for a in arenas if a.trainable):
+        ar.wait_update()  # a side-stream optimizer update (--overlap) may still be writing
+        if ar.numel > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(1000 + i)
+            n_blocks = DUMP_SAMPLE // DUMP_BLOCK
+            starts = torch.randint(0, ar.numel - DUMP_BLOCK + 1, (n_blocks,), generator=g).sort().values.tolist()
+        else:
+            starts = None
+        for kind, buf in (("param", ar.flat), ("grad", ar.grad_flat)):
+            part = buf if starts is None else torch.cat([buf[s:s + DUMP_BLOCK] for s in starts])
+            np.save(os.path.join(out_dir, f"{kind}_{ar.name}.npy"), part.float().cpu().numpy())
 
 
 
@@ -712,7 +762,9 @@ def main(argv=None):
     if args.launch_probe:
         return launch_probe(args, world)
     names = [n for n in args.sub_workloads.split(",") if n]
-    if world == 1 and not args.no_sub and args.workload == "step" and names:
+    if args.dump_outputs and args.workload != "step":
+        sys.exit("bench.py: --dump-outputs covers the training step only (--workload step)")
+    if world == 1 and args.full and not args.no_sub and args.workload == "step" and names:
         subs = run_sub_workloads(args, names)  # before this process touches the GPU
     if args.workload == "vit":
         if args.batch == 8:
@@ -767,34 +819,40 @@ def main(argv=None):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
 
-    # then a separate traced pass for the roofline: every GEMM launch bracketed by HIP events on the
-    # stream it runs on (the roofline object reports the kernel with the largest share of GPU time),
-    # HIP events around every decoder layer's forward and backward, the exchange's exposure events
-    traced_steps = max(1, min(args.steps, 3))
-    ops.trace_gemm("all")
-    from cullavo_amd import functions as F
-    F.trace_layers(True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, cm.arenas.values())
+
+    fams, exchange, traced_elapsed = None, None, 0.0
     reducer = tr.accel.reducer
-    if reducer is not None:
-        reducer.measure = True
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(traced_steps):
-        loss = step()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    traced_elapsed = time.perf_counter() - t1
-    launches = ops.trace_launches()  # (stops the tracing)
-    spans = F.layer_spans()
-    fams = gemm_families(launches)
-    exchange = None
+    if args.full:
+        # then a separate traced pass for the roofline: every GEMM launch bracketed by HIP events on
+        # the stream it runs on (the roofline object reports the kernel with the largest share of GPU
+        # time), HIP events around every decoder layer's forward and backward, the exchange's
+        # exposure events
+        traced_steps = max(1, min(args.steps, 3))
+        ops.trace_gemm("all")
+        from cullavo_amd import functions as F
+        F.trace_layers(True)
+        if reducer is not None:
+            reducer.measure = True
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(traced_steps):
+            loss = step()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        traced_elapsed = time.perf_counter() - t1
+        launches = ops.trace_launches()  # (stops the tracing)
+        spans = F.layer_spans()
+        fams = gemm_families(launches)
     if world > 1:
         t = torch.tensor([elapsed, traced_elapsed], device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, traced_elapsed = t[0].item(), t[1].item()
+    if world > 1 and args.full:
         st = reducer.exposure_stats() if reducer is not None else None
         # the exposed-exchange figure is the slowest rank's too
         e = torch.tensor([st["exposed_ms"] if st else -1.0, st["host_rendezvous_ms"] if st else -1.0],
@@ -816,11 +874,6 @@ def main(argv=None):
     samples = world * args.batch * args.steps
     value = samples / elapsed
     step_tflops = fl["train"] * world * args.batch / (elapsed / args.steps) / 1e12
-    top = fams[0]
-    kname = top["kernel"]
-    traffic, mfma_busy = measured_traffic(kname, workload_key(args))
-    achieved = top["achieved_tflops"]
-    n_launch = top["launches"]
     if rank == 0:
         line = {
             "metric": "train-step samples/sec (336px img + 512-tok prompt, 7B LM)" if "13b" not in args.config
@@ -846,7 +899,14 @@ def main(argv=None):
             "model_tflops_per_gpu": round(step_tflops / world, 2),
             "mfu": round(step_tflops / world / PEAK_BF16_TFLOPS, 4),
             "loss": round(loss_v, 5),
-            "roofline": {
+        }
+        if args.full:
+            top = fams[0]
+            kname = top["kernel"]
+            traffic, mfma_busy = measured_traffic(kname, workload_key(args))
+            achieved = top["achieved_tflops"]
+            n_launch = top["launches"]
+            line["roofline"] = {
                 "kernel": f"{kname}: {top['role']}, {len(top['shapes'])} shapes "
                           f"{['x'.join(map(str, sh)) for sh in top['shapes']]} (M x N x K), "
                           f"{n_launch // traced_steps} launches/step, {100 * top['ms'] / (traced_elapsed * 1e3):.1f} % of "
@@ -864,33 +924,32 @@ def main(argv=None):
                 "avg_ms": round(top["ms"] / n_launch, 4),
                 "launches_timed": n_launch,
                 "flops_per_launch": top["flops"] / n_launch,
-            },
-            "gemm_kernels": [{"kernel": f["kernel"], "role": f["role"],
-                              "share_of_step": round(f["ms"] / (traced_elapsed * 1e3), 4),
-                              "achieved_tflops": round(f["achieved_tflops"], 1),
-                              "frac": round(f["achieved_tflops"] / PEAK_BF16_TFLOPS, 4)} for f in fams[:6]],
-            "gemm_shapes": gemm_shapes(launches, traced_steps),
-            "traced_pass": {"steps": traced_steps, "ms_per_step": round(traced_elapsed / traced_steps * 1e3, 3),
-                            "what": "roofline, gemm_kernels, gemm_shapes and layer_roofline come from this separate "
-                                    "pass with HIP events around every GEMM launch and decoder layer; value and "
-                                    "ms_per_step from the untraced timed loop"},
-        }
-        if world == 1:
-            # every family's largest shape in isolation against hipBLASLt, same process: the
-            # library ceiling per family, and the isolated rate beside the in-step one (in the
-            # step, launches can share the GPU with the optimizer's side-stream update)
-            for f, entry in zip(fams[:6], line["gemm_kernels"]):
-                entry["library_ceiling"] = gemm_ceiling(f)
-            line["roofline"]["library_ceiling"] = line["gemm_kernels"][0]["library_ceiling"]
-        lr = layer_roofline(spans, fl, args, cfg.text_config)
-        if lr is not None:
-            line["layer_roofline"] = lr
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(cfg, args.text_len, args.cpu_seconds)
-        if subs is not None:
-            line["workloads"] = subs
-        if exchange is not None:
-            line["exchange"] = exchange
+            }
+            line["gemm_kernels"] = [{"kernel": f["kernel"], "role": f["role"],
+                                     "share_of_step": round(f["ms"] / (traced_elapsed * 1e3), 4),
+                                     "achieved_tflops": round(f["achieved_tflops"], 1),
+                                     "frac": round(f["achieved_tflops"] / PEAK_BF16_TFLOPS, 4)} for f in fams[:6]]
+            line["gemm_shapes"] = gemm_shapes(launches, traced_steps)
+            line["traced_pass"] = {"steps": traced_steps, "ms_per_step": round(traced_elapsed / traced_steps * 1e3, 3),
+                                   "what": "roofline, gemm_kernels, gemm_shapes and layer_roofline come from this "
+                                           "separate pass with HIP events around every GEMM launch and decoder layer; "
+                                           "value and ms_per_step from the untraced timed loop"}
+            if world == 1:
+                # every family's largest shape in isolation against hipBLASLt, same process: the
+                # library ceiling per family, and the isolated rate beside the in-step one (in the
+                # step, launches can share the GPU with the optimizer's side-stream update)
+                for f, entry in zip(fams[:6], line["gemm_kernels"]):
+                    entry["library_ceiling"] = gemm_ceiling(f)
+                line["roofline"]["library_ceiling"] = line["gemm_kernels"][0]["library_ceiling"]
+            lr = layer_roofline(spans, fl, args, cfg.text_config)
+            if lr is not None:
+                line["layer_roofline"] = lr
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(cfg, args.text_len, args.cpu_seconds)
+            if subs is not None:
+                line["workloads"] = subs
+            if exchange is not None:
+                line["exchange"] = exchange
         emit(line, args)
     if world > 1:
         dist.destroy_process_group()

@@ -77,6 +77,49 @@ def test_emit_writes_sidecar_and_prints_one_compact_last_line(tmp_path, capsys):
     assert line["detail"].endswith("detail.json")
 
 
+def test_plain_record_keeps_the_headline_and_writes_no_default_sidecar(capsys):
+    """a run without --full: the record is the headline alone; no roofline object, no sidecar"""
+    full = _full()
+    plain = {k: full[k] for k in bench.HEAD_KEYS if k in full}
+    args = bench.parse(["--gpus", "1", "--steps", "4", "--warmup", "1"])
+    assert not args.full and not args.dump_outputs
+    bench.emit(plain, args)
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] == full[k], k
+    assert "roofline" not in line and "detail" not in line and "workloads" not in line
+
+
+def test_dump_outputs_writes_the_same_seeded_float32_samples_each_time(tmp_path):
+    import numpy as np
+    import torch
+
+    from cullavo_amd.arena import ParamArena
+
+    big = ParamArena("layers", [("w", (1024, 1025)), ("b", (1025,))], device="cpu", trainable=True)
+    small = ParamArena("head", [("w", (7, 3))], device="cpu", trainable=True)
+    frozen = ParamArena("vision", [("w", (4, 4))], device="cpu")
+    g = torch.Generator().manual_seed(3)
+    for ar in (big, small):
+        ar.flat.copy_(torch.randn(ar.numel, generator=g))
+        ar.grad_flat.copy_(torch.randn(ar.numel, generator=g))
+    assert big.numel > bench.DUMP_SAMPLE
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(2.5), [big, frozen, small])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grad_head.npy", "grad_layers.npy", "loss.npy", "param_head.npy", "param_layers.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [2.5]
+    assert np.array_equal(np.load(tmp_path / "a" / "param_head.npy"), small.flat.float().numpy())
+    s = np.load(tmp_path / "a" / "grad_layers.npy")
+    assert s.shape == (bench.DUMP_SAMPLE,) and np.isin(s, big.grad_flat.float().numpy()).all()
+
+
 def test_layer_roofline_flops():
     from cullavo_amd.config import llava_1_5_7b
     from cullavo_amd.perf import flops_per_sample

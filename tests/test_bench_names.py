@@ -42,6 +42,7 @@ def test_gemm_kernel_names_of_the_step_shapes(shape, name, monkeypatch):
     ("gemm256pd_k<*, 288> M-split", "void (anonymous namespace)::gemm256pd_k<2, 288>(cvgemm::GemmArgs)", True),
     ("gemm256pd_k<*, 288> M-split", "void (anonymous namespace)::gemm256pd_k<2, 256>(cvgemm::GemmArgs)", False),
     ("gemm256p_k<MODE>", "void (anonymous namespace)::gemm256p_k<1>(cvgemm::GemmArgs)", True),
-])
+], ids=["g256-epi-wildcard-matches-epi2", "g256-epi-wildcard-rejects-other-layout", "g256pd-288-matches-288",
+        "g256pd-288-rejects-256", "g256p-mode-matches-mode1"])  # the rocprof names hold "::", which a test id cannot
 def test_pmc_family_pattern(family, rocprof, match):
     assert bool(pmc_family.name_pattern(family).search(rocprof)) == match

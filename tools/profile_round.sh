@@ -10,7 +10,7 @@ OUT=gpurun_out/${1:-prof}
 WL=${2:-config3-full}
 KERNEL=${3:-"gemm256_k<1, 1, 1, 256, 256, 0>"}
 shift 3 || true
-ARGS="--no-sub --no-cpu-baseline $*"
+ARGS="--full --no-sub --no-cpu-baseline $*"  # --full: the traced line names the roofline kernel (RK below)
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python bench.py --steps 3 --warmup 1 $ARGS > $OUT/bench_traced.log 2>&1
