@@ -70,15 +70,21 @@ class CuLLaVOModel(nn.Module):
 
     @classmethod
     def from_pretrained(cls, path: str, *, device="cuda", trainable: str = "full", lora: LoraSettings | None = None,
-                        **kw) -> "CuLLaVOModel":
+                        load_in_4bit: bool = False, **kw) -> "CuLLaVOModel":
         """llava-hf checkpoint directory (config.json + *.safetensors, ~4.37 or >= 4.45 key
-        layout) -> model, streamed into HBM (reference cullavo/load_cullavo.py:86)."""
+        layout) -> model, streamed into HBM (reference cullavo/load_cullavo.py:86).
+        load_in_4bit: the reference's prepare_cullavo(bits=4) numerics (load_cullavo.py:66-83): the
+        decoder layers' Linear weights become NF4 after loading (quant.quantize_lm_nf4_; lm_head,
+        projector and vision tower stay bf16); the report is kept as model.nf4_report."""
         from .checkpoint import load_llava_safetensors
         m = cls(CuLLaVOConfig.from_json(path), device=device, trainable=trainable, init="none", lora=lora)
         if "lora" in m.arenas:
             from .lora import init_lora_
             init_lora_(m.arenas["lora"], kw.get("seed", 0))
         load_llava_safetensors(m, path)
+        if load_in_4bit:
+            from .quant import quantize_lm_nf4_
+            m.nf4_report = quantize_lm_nf4_(m)
         return m
 
     # -- reference API -------------------------------------------------------------------------

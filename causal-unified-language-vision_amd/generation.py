@@ -42,6 +42,9 @@ FUSE_DECODE_NORMS = "norm" in _FUSE
 FUSE_DECODE_SWIGLU = "swiglu" in _FUSE
 FUSE_DECODE_GU = "gu" in _FUSE
 FUSE_DECODE_ROPE = "rope" in _FUSE
+# CULLAVO_NF4_DECODE=0: a model quantised by quant.quantize_lm_nf4_ decodes through the bf16 GEMV on
+# its (dequantised) arena weights instead of the 4-bit product on the NF4 copies (A/B switch)
+NF4_DECODE = os.environ.get("CULLAVO_NF4_DECODE", "1") != "0"
 
 
 class KVCache:
@@ -125,6 +128,16 @@ class KVCache:
         return cache
 
 
+def _nf4_linear(q, x, w, group, residual=None):
+    """One Linear of the decode step: on the NF4 copy q = (codes, absmax) when the layer has one
+    (the LoRA term materialised and passed as the epilogue addend; w goes along, so a shape on which
+    the bf16 GEMV measured faster stays there, ops.NF4_BF16_FASTER), else ops.linear on w."""
+    t, _ = group.forward(x, False, 0)
+    if q is None:
+        return ops.linear(x, w, residual=residual, addend=t)
+    return ops.nf4_decode_linear(x, q[0], q[1], residual=residual, addend=None if t is None else t.materialize(), w=w)
+
+
 def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int, start, kv_len,
                 attn_len: int | None = None):
     """One LlamaDecoderLayer over Lnew new rows per sequence (prefill: Lnew = prompt length on an
@@ -134,21 +147,27 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int,
     d, H, D = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim
     lg = layer.lora_groups
     B = sctx.B
+    # the layer's NF4 weight copies (quant.quantize_lm_nf4_; empty: none, or stale and dropped): the
+    # decode rows' products stream 4.5 bits per weight (cullavo_nf4_decode_linear), whatever
+    # FUSE_DECODE_NORMS / FUSE_DECODE_SWIGLU say; a weight left bf16 (K % 64 != 0) takes ops.linear
+    nf4 = {}
+    if NF4_DECODE and Lnew == 1 and h.dtype == torch.bfloat16 and h.shape[0] <= 16:
+        from .quant import nf4_weights
+        nf4 = nf4_weights(layer)
     # FUSE_DECODE_NORMS: the RMSNorms inside the q|k|v and gate|up weight-streaming products
     # (cullavo_decode_linear transform 1 / 4: every workgroup normalises the rows once into LDS; the
     # round-4 per-fragment form was ~2x slower, profiles/r04/decode/decode_fusions_ab.txt) for the
     # rows that fit LDS (M (d + 8) * 2 <= 64 KiB); FUSE_DECODE_SWIGLU: the SwiGLU in down_proj's
     # X loads (transform 2), only without FUSE_DECODE_GU. All bitwise the unfused values.
     fused = (FUSE_DECODE_NORMS and Lnew == 1 and h.shape[0] <= 16 and h.shape[0] * (d + 8) * 2 <= 65536
-             and h.dtype == torch.bfloat16
+             and h.dtype == torch.bfloat16 and not nf4
              and all(g is NO_LORA for g in lg.values()))
     if fused:
         qkv = ops.decode_linear(h, layer.w_qkv(), transform=1, norm_w=layer.input_layernorm.weight,
                                 eps=cfg.rms_norm_eps)
     else:
         x1, _ = ops.rmsnorm_fwd(h, layer.input_layernorm.weight, cfg.rms_norm_eps)
-        t, _ = lg["qkv"].forward(x1, False, 0)
-        qkv = ops.linear(x1, layer.w_qkv(), addend=t)
+        qkv = _nf4_linear(nf4.get("qkv"), x1, layer.w_qkv(), lg["qkv"])
     q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
     if Lnew == 1 and qkv.dtype == torch.bfloat16 and FUSE_DECODE_ROPE:
         # decode: RoPE, the cache append and attention in one pass (the cache row is start[b])
@@ -169,8 +188,7 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int,
         o = ops.attn_decode(q, cache.k[li], cache.v[li], kv_len, B=B, H=H, D=D,
                             max_len=attn_len if attn_len is not None else cache.length + 1,
                             scale=D ** -0.5, kv_start=sctx.kv_start)
-    t, _ = lg["o"].forward(o, False, 0)
-    h2 = ops.linear(o, layer.self_attn.o_proj.weight, residual=h, addend=t)
+    h2 = _nf4_linear(nf4.get("o"), o, layer.self_attn.o_proj.weight, lg["o"], residual=h)
     if fused:
         if FUSE_DECODE_GU:  # RMSNorm, gate|up product and SwiGLU in one launch (transform 4)
             a = ops.decode_linear(h2, layer.w_gu(), transform=4, norm_w=layer.post_attention_layernorm.weight,
@@ -183,13 +201,17 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int,
         return ops.linear(ops.swiglu_fwd(gu), layer.mlp.down_proj.weight, residual=h2)
     x2, _ = ops.rmsnorm_fwd(h2, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
     t, _ = lg["gu"].forward(x2, False, 0)
-    if FUSE_DECODE_GU and t is None and Lnew == 1 and x2.shape[0] <= 16 and x2.dtype == torch.bfloat16:
+    if "gu" in nf4:
+        if t is None:  # gate|up product + SwiGLU in one launch
+            a = ops.nf4_decode_linear(x2, *nf4["gu"], swiglu_out=True, w=layer.w_gu())
+        else:
+            a = ops.swiglu_fwd(ops.nf4_decode_linear(x2, *nf4["gu"], addend=t.materialize(), w=layer.w_gu()))
+    elif FUSE_DECODE_GU and t is None and Lnew == 1 and x2.shape[0] <= 16 and x2.dtype == torch.bfloat16:
         a = ops.decode_linear(x2, layer.w_gu(), transform=3)  # gate|up product + SwiGLU, one launch
     else:
         gu = ops.linear(x2, layer.w_gu(), addend=t)
         a = ops.swiglu_fwd(gu)
-    t, _ = lg["down"].forward(a, False, 0)
-    return ops.linear(a, layer.mlp.down_proj.weight, residual=h2, addend=t)
+    return _nf4_linear(nf4.get("down"), a, layer.mlp.down_proj.weight, lg["down"], residual=h2)
 
 
 class DecodeGraph:
@@ -212,6 +234,10 @@ class DecodeGraph:
         self.pos = cache.next_pos.to(torch.int64).clone()
         self.start = torch.full((B,), cache.length, dtype=torch.int32, device=dev)
         self.embed = model.get_input_embeddings()
+        # the captured kernels hold raw pointers into the layers' NF4 copies: keep the tensors alive
+        # for the graph's lifetime even if quant.nf4_weights() drops them from the layers meanwhile
+        from .quant import nf4_weights
+        self.nf4_refs = [nf4_weights(layer) for layer in lm.model.layers] if NF4_DECODE else []
         self.graph = torch.cuda.CUDAGraph()
         self.steps_left = cache.max_len - cache.length
         stream = torch.cuda.Stream(device=dev)

@@ -4,7 +4,8 @@ What the reference trains (cullavo/load_cullavo.py:94-112, :128-138): peft LoRA 
 lora_alpha=16, lora_dropout=0.05, bias='none' on every Linear of the language model except
 lm_head (find_all_linear_names, :8-20) and on every Linear of the vision tower except out_proj
 in encoder layers 12-22 (layers_to_transform, :101); plus projector, lm_head and embed_tokens.
-The base weights are frozen (the reference keeps them in NF4; here they stay bf16 in HBM).
+The base weights are frozen (the reference keeps them in NF4; here they are bf16 in HBM, holding
+the NF4-dequantised values after quant.quantize_lm_nf4_ / from_pretrained(load_in_4bit=True)).
 
 peft's LoraLayer on an nn.Linear (peft, un-vendored and absent here, restated from its
 published algorithm; oracle/cullavo_oracle.py:lora_linear is the CPU restatement):

@@ -22,6 +22,7 @@ __all__ = [
     "im2col_patches", "vision_embed_ln", "merge_plan", "row_gather2", "shift_targets", "ce_fwd",
     "ce_reduce", "ce_bwd", "adamw", "sumsq", "clip_coef", "scale_inplace", "kv_append", "attn_decode",
     "clip_image_preprocess", "visimage_geometry", "draw_boxes",
+    "nf4_quantize", "nf4_dequantize", "nf4_decode_linear",
 ]
 
 _DT = {torch.bfloat16: DT_BF16, torch.float32: DT_F32}
@@ -367,6 +368,104 @@ def decode_linear(x, w, *, transform: int = 0, norm_w=None, eps: float = 0.0, re
     y = torch.empty((M, N), dtype=x.dtype, device=x.device)
     call("decode_linear", int(transform), M, N, K, _ptr(x), _ld(x), _ptr(norm_w), float(eps), _ptr(w), _ld(w),
          _ptr(y), _ld(y), _ptr(residual), _ld(residual) if residual is not None else 0, _stream())
+    return y
+
+
+# ---- NF4 base weights (csrc/nf4.hip) -----------------------------------------------------------
+def nf4_quantize(w):
+    """w [N, K] bf16 (K % 64 == 0) -> (codes uint8 [N, K/2], absmax f32 [N, K/64]): QLoRA's NF4 with
+    64-element blocks along K, element 2i in the high nibble of byte i, no double quantisation."""
+    _dev(w)
+    if w.dtype != torch.bfloat16:
+        raise TypeError(f"nf4_quantize: bf16 weights only, got {w.dtype}")
+    N, K = w.shape
+    codes = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    absmax = torch.empty((N, K // 64), dtype=torch.float32, device=w.device)
+    call("nf4_quantize", N, K, _ptr(w), _ld(w), _ptr(codes), _ptr(absmax), _stream())
+    return codes, absmax
+
+
+def _nf4_check(codes, absmax):
+    if codes.dtype != torch.uint8 or absmax.dtype != torch.float32 or codes.dim() != 2 or absmax.dim() != 2:
+        raise TypeError("nf4: codes uint8 [N, K/2] and absmax f32 [N, K/64]")
+    if not (codes.is_contiguous() and absmax.is_contiguous()):
+        raise ValueError("nf4: codes and absmax must be contiguous")
+    N, K = codes.shape[0], codes.shape[1] * 2
+    if K % 64 != 0 or tuple(absmax.shape) != (N, K // 64):
+        raise ValueError(f"nf4: codes {tuple(codes.shape)} need K % 64 == 0 and absmax [{N}, K/64], "
+                         f"got {tuple(absmax.shape)}")
+    return N, K
+
+
+def nf4_dequantize(codes, absmax, out=None):
+    """bf16(L[code] * absmax) as w [N, K] bf16 (written into `out`, a 2-D bf16 view, when given)."""
+    _dev(codes, absmax, out)
+    N, K = _nf4_check(codes, absmax)
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.bfloat16, device=codes.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (N, K):
+        raise ValueError(f"nf4_dequantize: out must be bf16 [{N}, {K}]")
+    call("nf4_dequantize", N, K, _ptr(codes), _ptr(absmax), _ptr(out), _ld(out), _stream())
+    return out
+
+
+# Shapes (weight rows, K) -> the largest M at which the NF4 product measured SLOWER than the bf16
+# GEMV on the dequantised weight (cold weights, tools/nf4_decode_bench.py; profiles/r07/nf4/
+# README_r07.txt): nf4_gemv_k is bound by its unpacking (VALU / LDS), not by the stream, so where
+# the bf16 GEMV already runs near the HBM rate the 3.55x fewer bytes buy nothing. Given the bf16
+# weight, nf4_decode_linear keeps these on the bf16 GEMV. Unmeasured shapes take the NF4 product.
+NF4_BF16_FASTER = {
+    (12288, 4096): 2,   # 7B q|k|v: 1.04 / 1.01 of the bf16 time at M = 1 / 2, 0.98 at 4, 0.89 at 16
+    (22016, 4096): 8,   # 7B gate|up: 1.04 / 1.03 / 1.03 / 1.01 at M = 1 / 2 / 4 / 8, 0.96 at 16
+}
+
+
+def nf4_prefers_bf16(rows: int, K: int, M: int) -> bool:
+    """True when the bf16 GEMV measured faster than the NF4 product on a [rows, K] weight at M rows"""
+    return M <= NF4_BF16_FASTER.get((rows, K), 0)
+
+
+def nf4_decode_linear(x, codes, absmax, *, residual=None, addend=None, swiglu_out: bool = False, w=None):
+    """Decode rows (M <= 16, bf16) on an NF4 weight through cullavo_nf4_decode_linear:
+    y = x @ dq(W).T with the LoRA term `addend` and `residual` added as ops.linear adds them;
+    swiglu_out: the weight is the fused gate|up [2N, K] and y [M, N] = SwiGLU(x @ dq(W).T).
+    w: the dequantised bf16 weight [rows, K] (the arena's), when the caller has it: a shape on
+    which the bf16 GEMV measured faster (NF4_BF16_FASTER) then runs there instead, on the
+    same values rounded to bf16."""
+    _dev(x, codes, absmax, residual, addend, w)
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"nf4_decode_linear: bf16 rows only, got {x.dtype}")
+    rows, K = _nf4_check(codes, absmax)
+    if x.dim() != 2 or x.shape[1] != K:
+        raise ValueError(f"nf4_decode_linear: x {tuple(x.shape)} against a weight with K = {K}")
+    M = x.shape[0]
+    if M > 16:
+        raise ValueError(f"nf4_decode_linear: 1 <= M <= 16 rows, got {M}")
+    if x.data_ptr() % 16 != 0:
+        raise ValueError("nf4_decode_linear: x must be 16-byte aligned")
+    N = rows // 2 if swiglu_out else rows
+    if swiglu_out and (residual is not None or addend is not None):
+        raise ValueError("nf4_decode_linear: the SwiGLU output takes no residual or addend")
+    for name, t in (("residual", residual), ("addend", addend)):
+        if t is None:
+            continue
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"nf4_decode_linear: {name} must be bf16, got {t.dtype}")
+        if tuple(t.shape) != (M, N):
+            raise ValueError(f"nf4_decode_linear: {name} {tuple(t.shape)}, expected {(M, N)}")
+        if t.data_ptr() % 8 != 0:
+            raise ValueError(f"nf4_decode_linear: {name} must be 8-byte aligned")
+    if w is not None:
+        if w.dtype != torch.bfloat16 or tuple(w.shape) != (rows, K):
+            raise ValueError(f"nf4_decode_linear: w must be the bf16 [{rows}, {K}] weight")
+        if nf4_prefers_bf16(rows, K, M):
+            if swiglu_out:
+                return decode_linear(x, w, transform=3)
+            return linear(x, w, residual=residual, addend=addend)
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    call("nf4_decode_linear", int(bool(swiglu_out)), M, N, K, _ptr(x), _ld(x), _ptr(codes), _ptr(absmax), _ptr(y),
+         _ld(y), _ptr(residual), _ld(residual) if residual is not None else 0, _ptr(addend),
+         _ld(addend) if addend is not None else 0, _stream())
     return y
 
 

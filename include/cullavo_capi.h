@@ -51,9 +51,10 @@ extern "C" {
 /* ABI version: bumped whenever an exported signature changes (2: cullavo_im2col_patches gained
    out_dtype, cullavo_vision_embed_ln dtype, cullavo_gemm_desc f32_operands; 4: the tuning switches
    of the measured-slower GEMM variants removed with them: cullavo_gemm_set_streamk,
-   cullavo_gemm_set_prefetch, cullavo_gemm_set_loaders). A consumer built against this header
+   cullavo_gemm_set_prefetch, cullavo_gemm_set_loaders; 5: the NF4 entry points cullavo_nf4_quantize,
+   cullavo_nf4_dequantize, cullavo_nf4_decode_linear added). A consumer built against this header
    checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
-#define CULLAVO_ABI_VERSION 4
+#define CULLAVO_ABI_VERSION 5
 
 int cullavo_abi_version(void);
 const char* cullavo_last_error(void);
@@ -384,6 +385,32 @@ int cullavo_kv_append(const void* k, int64_t ldk, const void* v, int64_t ldv, vo
 int cullavo_decode_linear(int x_transform, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
                           const void* norm_w, float eps, const void* W, int64_t ldw, void* y, int64_t ldy,
                           const void* residual, int64_t ldr, void* stream);
+/* ---- NF4 base weights (ABI 5) ----------------------------------------------------------------
+ * The reference's LM never runs on bf16 base weights: every decoder-layer Linear is bitsandbytes
+ * NF4 with bf16 compute, lm_head and the projector skipped (cullavo/load_cullavo.py:66-83). The
+ * format here (csrc/nf4.hip; INTEGRATION.md "NF4"): blocks of 64 consecutive k of one row of
+ * W [N, K], K % 64 == 0; absmax f32 [N, K/64] = max |w| of the block (an all-zero block: 0, code 7
+ * everywhere); code = the number of midpoints (L[j] + L[j+1]) / 2 of QLoRA's 16-entry code book L
+ * below f32(w) / absmax; codes uint8 [N, K/2] row-major, element 2i in the high nibble of byte i
+ * (bitsandbytes' order); dequantised value bf16(L[code] * absmax). No double quantisation.
+ * cullavo_nf4_quantize: W bf16 (row stride ldw) -> codes, absmax, one pass.
+ * cullavo_nf4_dequantize: codes, absmax -> W bf16 (row stride ldw). */
+int cullavo_nf4_quantize(int64_t N, int64_t K, const void* W, int64_t ldw, void* codes, void* absmax,
+                         void* stream);
+int cullavo_nf4_dequantize(int64_t N, int64_t K, const void* codes, const void* absmax, void* W, int64_t ldw,
+                           void* stream);
+/* The decode step's product on NF4 weights (the 4-bit model's generate(), reference
+ * cullavo/load_cullavo.py:66-83 + cullavo/arch_cullavo.py:605-636): y[M,N] = x dq(W)^T for
+ * M <= 16 rows of x [M,K] bf16, f32 accumulation per 64-block of the code-book values (to 2^-18
+ * relative), scaled by the block's absmax in f32 -- the weights are not rounded to bf16 first.
+ * Epilogue as cullavo_gemm_ex: y = bf16(bf16(bf16(acc) + addend) + residual) (either nullable).
+ * swiglu_out 1: codes / absmax hold the fused gate|up weight's 2N rows and y[M,N] =
+ * SwiGLU(x dq(W)^T) as cullavo_decode_linear's transform 3 (no residual, no addend).
+ * N % 8 == 0, K % 64 == 0, strides multiples of 8 (ld_addend: 4). Deterministic. */
+int cullavo_nf4_decode_linear(int swiglu_out, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
+                              const void* codes, const void* absmax, void* y, int64_t ldy,
+                              const void* residual, int64_t ldr, const void* addend, int64_t ld_addend,
+                              void* stream);
 size_t cullavo_attn_decode_workspace(int B, int H, int max_len, int D);
 int cullavo_attn_decode(const void* q, int64_t ldq, const void* k_cache, const void* v_cache, int64_t ld_tok,
                         int64_t ld_batch, const int32_t* kv_len, const int32_t* kv_start, void* o, int64_t ldo,
