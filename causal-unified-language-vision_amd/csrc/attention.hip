@@ -88,66 +88,22 @@ DEV frag8 pack_frag(const f32x16& a, int s) {
   return f;
 }
 
-// Forward tile rows are read with 16-B buffer loads whose range check zero-fills rows past nrows
-// (one select per chunk instead of a branch around every load; ~13 % fewer VALU instructions in
-// the forward loop, 5-7 % faster forward on the MI355X, tools/attn_bench.py ATTN_STAGE_AB). The buffer covers one (batch, head) slice of the tensor, so
-// its byte offsets fit 32 bits unless nrows * ld is very large; then the pointer path runs.
-constexpr unsigned kOOB = 0x7FFFFFF0u;
-
 __device__ float g_rescale_thr = 8.f;  // forward's deferred-rescale threshold (cullavo_attn_set_rescale)
-// forward staging (cullavo_attn_set_stage): 0 = pointer loads behind a bounds branch, 1 = per-chunk
-// range-checked buffer loads, 2 = per-tile descriptor (StageT), 3 = 2 + s_setprio, 4 = LDS-DMA
-// (StageDMA, the default since round 3: 138.3 -> 132.0 us on the 7B layer, 153.3 -> 141.9 us on
-// the ViT bs-64 layer, alternating on one MI355X, profiles/r03/s3a/attn_bench.txt), 5 = 4 with
-// inline-asm fragment groups (131.7 / 141.1 us: within noise of 4, kept as an A/B), 7 = the
-// software-pipelined kernel attn_fwd_pipe_k (round 4); -1 (default) = 7 (with its widened O
-// stores: 7B layer 151 -> 124-128 us, ViT bs-64 layer 148-154 -> 139-144 us alternating on one
-// box, profiles/r04/attn/attn_fwd_ab.txt)
+// forward kernel (cullavo_attn_set_stage): 4 = attn_fwd_k, the plain LDS-DMA kernel; 7 = the
+// software-pipelined attn_fwd_pipe_k, bitwise equal to 4; -1 (default) = 7 (7B layer 151 ->
+// 124-128 us, ViT bs-64 layer 148-154 -> 139-144 us alternating on one box,
+// profiles/r04/attn/attn_fwd_ab.txt). The register-staged forms 0-3 and the inline-asm form 5 of
+// rounds 2-3 left with ABI 6 ("measured, not kept")
 int g_fwd_stage = -1;
-// backward staging (cullavo_attn_set_bwd_stage): bit 0 = dK/dV Q / dO by LDS-DMA, bit 1 = the
-// dQ-from-dS kernel's K / dS^T by LDS-DMA (else registers, StageT), bit 2 = the 4-stage LDS-DMA
-// ring dQ kernel attn_bwd_dq_ring_k (D = 128; round 6, takes precedence over bit 1), bit 3 = the
-// blocked dS^T layout (ds_layout). Round 5: with bit 0 the dK/dV kernel reads every fragment by
-// inline asm one step ahead of its MFMAs (no vmcnt(0) in front of the reads, the dS^T stores left
-// in flight at the tile's end): 7B layer backward 467.5 -> 449.7 us, bitwise equal
-// (profiles/r05/attn/attn_bwd_stage_ab.txt), so bit 0 is the default.
-//
-// ds_layout: the mode-7 dS^T workspace [B H][LkP][LqP] bf16 is stored either row-major (key rows of
-// LqP queries: a dQ tile of 64 keys x 128 queries is 64 runs of 256 B, 2 LqP bytes apart) or
-// blocked by 128-query column blocks ([B H][LqP / 128][LkP][128]: the same tile is one contiguous
-// 16 KiB run). Same bytes, same values; the address is bh st_bh + (q / 128) st_blk + key ldst + q % 128
-int g_bwd_stage = 1;
 
-DEV bool buf_ok(int64_t ld, int nrows, int D) { return ((int64_t)nrows * ld + D) * 2 < (int64_t)kOOB; }
-
-DEV __amdgpu_buffer_rsrc_t tile_rsrc(const u16* base, int64_t ld, int nrows, int D) {
-  const int64_t bytes = nrows > 0 ? ((int64_t)(nrows - 1) * ld + D) * 2 : 0;
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)bytes, 0x00020000);
-}
-
-DEV u16x8 buf_row_load(__amdgpu_buffer_rsrc_t rs, int64_t ld, int row0, int nrows, int row, int ch) {
-  const int gr = row0 + row;
-  const unsigned off = gr < nrows ? (unsigned)(gr * (unsigned)ld + ch * 8) * 2u : kOOB;
-  return __builtin_bit_cast(u16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-}
-
-// global -> registers -> LDS staging of a [ROWS][D] tile of a [L, H, D]-strided tensor
-// BUF: buffer loads (attn_fwd_k; measured neutral to slightly slower in the backward kernels)
-template <int ROWS, int D, bool BUF = false>
+// global -> registers -> LDS staging of a [ROWS][D] tile of a [L, H, D]-strided tensor (the
+// 4-wave backward kernels)
+template <int ROWS, int D>
 struct Stage {
   static constexpr int kChunks = ROWS * D / 8;
   static constexpr int kPer = kChunks / 256;  // 16-byte chunks per thread
   u16x8 r[kPer];
   DEV void load(const u16* base, int64_t ld, int row0, int nrows) {
-    if (BUF && buf_ok(ld, nrows, D)) {
-      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(base, ld, nrows, D);
-#pragma unroll
-      for (int i = 0; i < kPer; ++i) {
-        const int q = threadIdx.x + 256 * i;
-        r[i] = buf_row_load(rs, ld, row0, nrows, q / (D / 8), q % (D / 8));
-      }
-      return;
-    }
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
       const int q = threadIdx.x + 256 * i;
@@ -166,14 +122,14 @@ struct Stage {
   }
 };
 
-// Per-tile descriptor staging (the forward's default, STAGE 2): the buffer descriptor is rebuilt
-// per tile from scalars (base advanced to the tile's first row, num_records covering only the
-// rows that exist, so rows past the sequence end read as zeros), every lane keeps ONE
+// Per-tile descriptor staging through registers (the dQ-from-dS^T kernel): the buffer descriptor is
+// rebuilt per tile from scalars (base advanced to the tile's first row, num_records covering only
+// the rows that exist, so rows past the sequence end read as zeros), every lane keeps ONE
 // loop-invariant byte offset, and the i-th chunk's row step (i * rows-per-pass * ld) is the
-// instruction's scalar offset: no per-tile VALU address arithmetic, compares or selects (the
-// per-chunk form kept 16 v_mul_lo_u32 + range selects in the loop and spilled 62 VGPRs).
-template <int ROWS, int D, int NT = 256>
+// instruction's scalar offset: no per-tile VALU address arithmetic, compares or selects.
+template <int ROWS, int D>
 struct StageT {
+  static constexpr int NT = 256;                  // threads of the workgroup
   static constexpr int kPer = ROWS * D / 8 / NT;  // 16-byte chunks per thread
   static constexpr int kPass = NT / (D / 8);      // rows covered by one pass of NT threads
   static_assert(kPer * NT * 8 == ROWS * D && NT % (D / 8) == 0, "tile must split evenly over the threads");
@@ -199,7 +155,7 @@ struct StageT {
   }
 };
 
-// LDS-DMA staging of a [ROWS][D] tile (the forward's STAGE 4): buffer_load ... lds writes each
+// LDS-DMA staging of a [ROWS][D] tile (attn_fwd_k, the 8-wave dK/dV kernel): buffer_load ... lds writes each
 // 1 KiB piece lane-linearly (lane i -> byte 16 i of the piece), so the kv_off XOR image is
 // produced by permuting the SOURCE chunk: the lane landing in slot s of image row r loads chunk
 // s ^ swizzle(r) (the swizzle is an involution). No staging VGPRs and no ds_write: the data goes
@@ -302,53 +258,6 @@ DEV void tie4t(s16x4& a, s16x4& b, s16x4& c, s16x4& d) {
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// Forward STAGE 5: the P V^T product's V^T fragments through inline-asm ds_read_b64_tr_b16 (one
-// group = the ND fragments of one 16-key slice, VB the slice's LDS byte offset as an immediate),
-// tied by a counted lgkmcnt wait (CNT = reads allowed to stay in flight: the next group's)
-template <int ND, unsigned VB>
-DEV void tr_group_issue(s16x4 (&lo)[ND], s16x4 (&hi)[ND], const unsigned (&toff)[ND][2]) {
-#pragma unroll
-  for (int dt = 0; dt < ND; ++dt)
-    asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4"
-                 : "=&v"(lo[dt]), "=&v"(hi[dt])
-                 : "v"(toff[dt][0]), "v"(toff[dt][1]), "n"(VB)
-                 : "memory");
-}
-template <int ND, int CNT>
-DEV void tr_group_tie(s16x4 (&lo)[ND], s16x4 (&hi)[ND]) {
-#pragma unroll
-  for (int dt = 0; dt < ND; ++dt)
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(lo[dt]), "+v"(hi[dt]) : "n"(CNT) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-// Forward STAGE 5, S = K Q^T: 4 K row fragments (k-steps S0..S0+3 at LDS byte offset OFF from
-// each lane's roff) by inline-asm ds_read_b128, tied by a counted lgkmcnt wait
-template <int NS, int S0, unsigned OFF>
-DEV void k_group_issue(s16x8 (&kf)[4], const unsigned (&roff)[NS]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(kf[j]) : "v"(roff[S0 + j]), "n"(OFF) : "memory");
-}
-template <int CNT>
-DEV void k_group_tie(s16x8 (&kf)[4]) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(kf[0]), "+v"(kf[1]), "+v"(kf[2]), "+v"(kf[3]) : "n"(CNT) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <int NS, int S0>
-DEV void k_group_mfma(const s16x8 (&kf)[4], const frag8 (&qf)[NS], f32x16& acc) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(frag8, kf[j]), qf[S0 + j], acc, 0, 0, 0);
-}
-template <int ND>
-DEV void tr_group_mfma(const s16x4 (&lo)[ND], const s16x4 (&hi)[ND], const frag8& pf, f32x16 (&o)[ND]) {
-#pragma unroll
-  for (int dt = 0; dt < ND; ++dt) {
-    const s16x8 v = __builtin_shufflevector(lo[dt], hi[dt], 0, 1, 2, 3, 4, 5, 6, 7);
-    o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(frag8, v), pf, o[dt], 0, 0, 0);
-  }
-}
-
 // two V^T fragments (column blocks DT0, DT0 + 1 of a 16-key slice at LDS offset VB) by inline asm,
 // tied by a counted lgkmcnt wait: the pipelined forward's P V reads in pairs (fewer registers in
 // flight than a whole slice: register pressure made the compiler spill in-flight fragments)
@@ -378,7 +287,10 @@ DEV void tr2_mfma(const s16x4 (&lo)[2], const s16x4 (&hi)[2], const frag8& pf, f
 // ============================================================================================
 // forward
 // ============================================================================================
-template <int D, bool CAUSAL, int STAGE, int PRIO = 0>
+// The plain kernel (cullavo_attn_set_stage(4)): a tile's three steps in program order, K / V tiles
+// by LDS-DMA into a double buffer. The readable statement of the arithmetic; attn_fwd_pipe_k below
+// is its bitwise twin and the default.
+template <int D, bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void attn_fwd_k(const u16* __restrict__ Q, int64_t ldq,
                                                      const u16* __restrict__ K, int64_t ldk,
                                                      const u16* __restrict__ V, int64_t ldv,
@@ -428,48 +340,17 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(const u16* __restrict__ Q, 
   const int ntiles = (kend + KT - 1) / KT;
   const int t0 = kstart / KT;
 
-  using St = std::conditional_t<STAGE == 2 || STAGE >= 4, StageT<KT, D>, Stage<KT, D, STAGE == 1>>;
-  St sk, sv;
-  unsigned vok = 0, vov = 0;
-  if constexpr (STAGE == 2) {
-    vok = StageT<KT, D>::lane_off(ldk);
-    vov = StageT<KT, D>::lane_off(ldv);
-  }
   StageDMA<KT, D, 4> dk_, dv_;
-  if constexpr (STAGE >= 4) {
-    dk_.prep(ldk, __builtin_amdgcn_readfirstlane(wave), lane);
-    dv_.prep(ldv, __builtin_amdgcn_readfirstlane(wave), lane);
-  }
-  // STAGE 4: K and V of the tile at row0 straight into LDS buffer pair i
+  dk_.prep(ldk, __builtin_amdgcn_readfirstlane(wave), lane);
+  dv_.prep(ldv, __builtin_amdgcn_readfirstlane(wave), lane);
+  // K and V of the tile at row0 straight into LDS buffer pair i (K at smem + 2*i*TILE, V right
+  // after it)
   auto dma_kv = [&](int row0, int i) {
     const int w = __builtin_amdgcn_readfirstlane(wave);
     dk_.issue(Kb, ldk, row0, Lk, smem + 2 * i * TILE, w);
     dv_.issue(Vb, ldv, row0, Lk, smem + 2 * i * TILE + TILE, w);
   };
-  auto load_kv = [&](int row0) {
-    if constexpr (STAGE == 2 || STAGE >= 4) {
-      sk.load(Kb, ldk, row0, Lk, vok);
-      sv.load(Vb, ldv, row0, Lk, vov);
-    } else {
-      sk.load(Kb, ldk, row0, Lk);
-      sv.load(Vb, ldv, row0, Lk);
-    }
-  };
-  // buffer i: K at smem + 2*i*TILE, V right after it
-#define bufK(i) (smem + 2 * (i) * TILE)
-#define bufV(i) (smem + 2 * (i) * TILE + TILE)
-  if (t0 < ntiles) {
-    if constexpr (STAGE == 6) {
-      dma_kv(t0 * KT, 0);
-      dma_kv(t0 * KT, 1);
-    } else if constexpr (STAGE >= 4) {
-      dma_kv(t0 * KT, 0);
-    } else {
-      load_kv(t0 * KT);
-      sk.store(bufK(0));
-      sv.store(bufV(0));
-    }
-  }
+  if (t0 < ntiles) dma_kv(t0 * KT, 0);
   // vmcnt(0) the compiler can see on every path: the Q fragments are then known to have
   // landed inside the loop, so the in-loop prefetch of the next K/V tile is not waited for
   // before the first MFMA (hipcc otherwise emits vmcnt(0) there: the prefetch is conditional)
@@ -501,65 +382,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(const u16* __restrict__ Q, 
   auto tile = [&](auto cur_c, int t) {
     constexpr int CUR = decltype(cur_c)::value;
     constexpr unsigned PAIR = 2u * CUR * TILE;
-    const bool more = t + 1 < ntiles;
-    if constexpr (STAGE == 6) {
-      // lab only (cullavo_attn_set_stage(6), WRONG results): no K/V loads after the first tile,
-      // every tile computes on the first tile's LDS -- the forward's time without its memory waits
-    } else if constexpr (STAGE >= 4) {
-      if (more) dma_kv((t + 1) * KT, CUR ^ 1);  // pair CUR^1 was last read before the previous barrier
-    } else {
-      if (more) load_kv((t + 1) * KT);
-    }
-    // PRIO (A/B, cullavo_attn_set_stage(3)): the two MFMA blocks at raised wave priority, so the
-    // SIMD's other wave (in its softmax) yields the issue slot to the MFMAs (guide T5)
-    if constexpr (PRIO) {
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    if (t + 1 < ntiles) dma_kv((t + 1) * KT, CUR ^ 1);  // pair CUR^1 was last read before the previous barrier
     // S^T = K Q^T for two 32-key halves
     f32x16 st[2];
-    if constexpr (STAGE == 5) {
-      // K fragments by inline-asm ds_read_b128 in groups of 4, the next group in flight while
-      // the current one's MFMAs issue (hipcc otherwise reads each fragment into one register
-      // quad right before its MFMA, exposing the LDS latency 16 times per tile)
-      st[0] = f32x16(0.f);
-      st[1] = f32x16(0.f);
-      s16x8 ka[4], kb[4];
-      if constexpr (NS == 8) {
-        k_group_issue<NS, 0, PAIR>(ka, roff);
-        k_group_issue<NS, 4, PAIR>(kb, roff);
-        k_group_tie<4>(ka);
-        k_group_mfma<NS, 0>(ka, qf, st[0]);
-        k_group_issue<NS, 0, PAIR + 32 * 2 * D>(ka, roff);
-        k_group_tie<4>(kb);
-        k_group_mfma<NS, 4>(kb, qf, st[0]);
-        k_group_issue<NS, 4, PAIR + 32 * 2 * D>(kb, roff);
-        k_group_tie<4>(ka);
-        k_group_mfma<NS, 0>(ka, qf, st[1]);
-        k_group_tie<0>(kb);
-        k_group_mfma<NS, 4>(kb, qf, st[1]);
-      } else {
-        k_group_issue<NS, 0, PAIR>(ka, roff);
-        k_group_issue<NS, 0, PAIR + 32 * 2 * D>(kb, roff);
-        k_group_tie<4>(ka);
-        k_group_mfma<NS, 0>(ka, qf, st[0]);
-        k_group_tie<0>(kb);
-        k_group_mfma<NS, 0>(kb, qf, st[1]);
-      }
-    } else {
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
       st[kt] = f32x16(0.f);
 #pragma unroll
       for (int s = 0; s < NS; ++s)
         st[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_frag(roff[s] + PAIR + kt * 32 * 2 * D), qf[s], st[kt], 0, 0, 0);
-    }
-    }
-    if constexpr (PRIO) {
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
     }
     // mask (boundary tiles only, branch-free), tile max on the raw scores (c > 0)
     const int kbase = t * KT;
@@ -613,30 +444,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(const u16* __restrict__ Q, 
     rs += __shfl_xor(rs, 32, 64);
     l += rs;
     // O^T += V^T P^T
-    if constexpr (PRIO) {
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (STAGE == 5) {
-      // V^T fragments by inline-asm ds_read_b64_tr_b16 (the builtin carries no memory operand,
-      // so hipcc puts vmcnt(0) -- the next tile's in-flight LDS-DMA -- in front of it), in four
-      // groups of ND fragments, the next group issued before the current one's MFMAs; a counted
-      // lgkmcnt wait ties each group's registers (DS operations complete in order)
-      s16x4 lo0[ND], hi0[ND], lo1[ND], hi1[ND];
-      tr_group_issue<ND, PAIR + 0 * 2 * D>(lo0, hi0, toff);
-      tr_group_issue<ND, PAIR + 16 * 2 * D>(lo1, hi1, toff);
-      tr_group_tie<ND, 2 * ND>(lo0, hi0);
-      tr_group_mfma<ND>(lo0, hi0, pack_frag(st[0], 0), o);
-      tr_group_issue<ND, PAIR + 32 * 2 * D>(lo0, hi0, toff);
-      tr_group_tie<ND, 2 * ND>(lo1, hi1);
-      tr_group_mfma<ND>(lo1, hi1, pack_frag(st[0], 1), o);
-      tr_group_issue<ND, PAIR + 48 * 2 * D>(lo1, hi1, toff);
-      tr_group_tie<ND, 2 * ND>(lo0, hi0);
-      tr_group_mfma<ND>(lo0, hi0, pack_frag(st[1], 0), o);
-      tr_group_tie<ND, 0>(lo1, hi1);
-      tr_group_mfma<ND>(lo1, hi1, pack_frag(st[1], 1), o);
-    } else {
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -647,26 +454,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(const u16* __restrict__ Q, 
         for (int dt = 0; dt < ND; ++dt)
           o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_tr_frag(toff[dt][0] + vb, toff[dt][1] + vb), pf, o[dt], 0, 0, 0);
       }
-    }
-    if constexpr (PRIO) {
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (STAGE >= 4) {
-      // the next pair's DMA has landed in LDS (vmcnt counts LDS-DMA), then every wave's
-      // reads of pair CUR are done before anyone overwrites it; the sched_barrier keeps the
-      // tile's MFMAs in front of the wait (hipcc otherwise sinks the last ones below it)
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    } else {
-      if (more) {
-        sk.store(bufK(CUR ^ 1));
-        sv.store(bufV(CUR ^ 1));
-      }
-      __syncthreads();
-    }
+    // the next pair's DMA has landed in LDS (vmcnt counts LDS-DMA), then every wave's reads of
+    // pair CUR are done before anyone overwrites it; the sched_barrier keeps the tile's MFMAs in
+    // front of the wait (hipcc otherwise sinks the last ones below it)
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
   };
   for (int t = t0; t < ntiles; t += 2) {
     tile(std::integral_constant<int, 0>{}, t);
@@ -690,7 +483,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(const u16* __restrict__ Q, 
 }
 
 // ============================================================================================
-// forward, software-pipelined (STAGE 7)
+// forward, software-pipelined (the default; cullavo_attn_set_stage(7))
 // ============================================================================================
 // attn_fwd_k runs a tile's three steps in order -- S = K Q^T on the matrix pipe, the softmax on
 // the VALU, P V on the matrix pipe -- so inside a wave the matrix pipe idles through the softmax
@@ -702,7 +495,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(const u16* __restrict__ Q, 
 // counted lgkmcnt wait (the fragment group after the current one stays in flight; hipcc puts a
 // vmcnt(0) -- the in-flight LDS-DMA -- in front of the builtin transposed read) and each
 // softmax chunk is pinned beside its MFMA group by sched_group_barrier. Per element the
-// arithmetic is attn_fwd_k's, in the same order: outputs bitwise equal to STAGE 4.
+// arithmetic is attn_fwd_k's, in the same order: outputs bitwise equal to its.
 // both wave halves' values of a per-query quantity combined (lane l with lane l ^ 32) by one
 // v_permlane32_swap on two registers holding x: afterwards one holds the lower half's values in
 // both halves, the other the upper half's. Inline asm, so the two operands are two registers: the
@@ -1149,13 +942,14 @@ __global__ __launch_bounds__(256) void attn_delta_k(const u16* __restrict__ O, i
 // 32-row query tiles staged in LDS. S = Q K^T and dP = dO V^T keep the key on the lane;
 // dV = P^T dO and dK = dS^T Q take P / dS straight from the accumulators (A operand) and
 // dO / Q as transposed LDS fragments.
-template <int D, bool CAUSAL, int QT>
+template <int D, bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_k(
     const u16* __restrict__ Q, int64_t ldq, const u16* __restrict__ K, int64_t ldk,
     const u16* __restrict__ V, int64_t ldv, const u16* __restrict__ dO, int64_t lddo,
     const float* __restrict__ LSE, const float* __restrict__ DELTA, u16* __restrict__ dK,
     int64_t lddk, u16* __restrict__ dV, int64_t lddv, int H, int Lq, int Lk, float scale,
     const int32_t* __restrict__ kv_start) {
+  constexpr int QT = 32;         // query rows per tile (64-row tiles lost the sweep on both head dims)
   constexpr int NSUB = QT / 32;  // 32-row query sub-tiles per barrier
   constexpr int TILE = QT * D * 2;
   constexpr int NS = D / 16;
@@ -1458,7 +1252,12 @@ struct StageN {
   }
 };
 
-template <int D, bool CAUSAL, bool DS_OUT = false, bool DMA = false>
+// Q / dO tiles arrive by LDS-DMA (no staging registers or ds_write), and every fragment is read by
+// inline asm one step ahead of its MFMAs: 7B layer backward 467.5 -> 449.7 us against the
+// register-staged form, bitwise equal (profiles/r05/attn/attn_bwd_stage_ab.txt). DS_OUT: also store
+// dS^T[b, h][key][q] for attn_bwd_dq_ds_k (mode 7); the workspace is row-major, ldst = LqP with
+// the 128-query block qb at column 128 qb (st_blk = 128).
+template <int D, bool CAUSAL, bool DS_OUT>
 __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_k(
     const u16* __restrict__ Q, int64_t ldq, const u16* __restrict__ K, int64_t ldk,
     const u16* __restrict__ V, int64_t ldv, const u16* __restrict__ dO, int64_t lddo,
@@ -1507,17 +1306,14 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_k(
   const int nqt = (Lq + QT - 1) / QT;
   const bool block_live = kmin < Lk && (kmin + KB > kstart);
 
-  StageT<QT, D, 512> sq, sdo;  // per-tile descriptors (see StageT)
-  const unsigned voq = StageT<QT, D, 512>::lane_off(ldq), vodo = StageT<QT, D, 512>::lane_off(lddo);
-  // DMA (cullavo_attn_set_bwd_stage(1)): Q / dO tiles by LDS-DMA into the swizzled image (as the
-  // forward's StageDMA), no staging registers or ds_write
+  // Q / dO tiles by LDS-DMA into the swizzled image (as the forward's StageDMA)
   StageDMA<QT, D, 8> dq_, ddo_;
-  // DMA: per-lane LDS byte offsets of the asm fragment reads (rows relative to a 32-row slice /
-  // a 16-key slice: the image swizzle depends on row & 15 only)
+  dq_.prep(ldq, wave, lane);
+  ddo_.prep(lddo, wave, lane);
+  // per-lane LDS byte offsets of the asm fragment reads (rows relative to a 32-row slice / a
+  // 16-key slice: the image swizzle depends on row & 15 only)
   unsigned roff_b[NS], toff_b[ND][2];
-  if constexpr (DMA) {
-    dq_.prep(ldq, wave, lane);
-    ddo_.prep(lddo, wave, lane);
+  {
 #pragma unroll
     for (int s = 0; s < NS; ++s) roff_b[s] = kv_off<D>(lane & 31, 2 * s + (lane >> 5));
     const int i = lane & 15, qq = i >> 2, pp = i & 3;
@@ -1552,15 +1348,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_k(
     skv.load(Vb, ldv, kmin, Lk);
     skv.store(sV);
     if (qt0 < nqt) {
-      if constexpr (DMA) {
-        dq_.issue(Qb, ldq, qt0 * QT, Lq, bufs, wave);
-        ddo_.issue(dOb, lddo, qt0 * QT, Lq, bufs + TQ, wave);
-      } else {
-        sq.load(Qb, ldq, qt0 * QT, Lq, voq);
-        sdo.load(dOb, lddo, qt0 * QT, Lq, vodo);
-        sq.store(bufs);
-        sdo.store(bufs + TQ);
-      }
+      dq_.issue(Qb, ldq, qt0 * QT, Lq, bufs, wave);
+      ddo_.issue(dOb, lddo, qt0 * QT, Lq, bufs + TQ, wave);
       load_aux(qt0);
       store_aux(bufs);
     }
@@ -1574,20 +1363,15 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_k(
     char* nbuf = bufs + (cur ^ 1) * BUF;
     const bool more = qt + 1 < nqt;
     if (more) {
-      if constexpr (DMA) {
-        dq_.issue(Qb, ldq, (qt + 1) * QT, Lq, nbuf, wave);  // nbuf was last read before the previous barrier
-        ddo_.issue(dOb, lddo, (qt + 1) * QT, Lq, nbuf + TQ, wave);
-      } else {
-        sq.load(Qb, ldq, (qt + 1) * QT, Lq, voq);
-        sdo.load(dOb, lddo, (qt + 1) * QT, Lq, vodo);
-      }
+      dq_.issue(Qb, ldq, (qt + 1) * QT, Lq, nbuf, wave);  // nbuf was last read before the previous barrier
+      ddo_.issue(dOb, lddo, (qt + 1) * QT, Lq, nbuf + TQ, wave);
       load_aux(qt + 1);
     }
     const float* slse = (const float*)(buf + 2 * TQ);
     const float* sdel = slse + QT;
     // S[q][key], dP[q][key] for this wave's 32 query rows of the tile
     f32x16 sacc = f32x16(0.f), pacc = f32x16(0.f);
-    if constexpr (DMA) {
+    {
       // inline-asm fragment reads (a compiler-visible LDS read may alias the next tile's in-flight
       // LDS-DMA, so hipcc would wait vmcnt(0) in front of it), one k-step ahead of the MFMAs: the
       // four reads of step s + 1 are in flight while step s's two MFMAs issue
@@ -1611,12 +1395,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_k(
         pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(frag8, d1), __builtin_bit_cast(frag8, v1), pacc, 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-    } else {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<D>(buf, 32 * u, s, lane), row_frag<D>(sK, 32 * ksl, s, lane), sacc, 0, 0, 0);
-      pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<D>(buf + TQ, 32 * u, s, lane), row_frag<D>(sV, 32 * ksl, s, lane), pacc, 0, 0, 0);
-    }
     }
     // query qq is live for this lane's key iff qlo <= qq < qlim: one unsigned compare per element
     const int qoff = qt * QT + 32 * u + 4 * hf - qlo;
@@ -1642,13 +1420,13 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_k(
         // dS^T[key][q] (the bf16 operand of dK) for the dQ kernel: registers 8s..8s+3 / 8s+4..8s+7
         // are query rows 16s + 4hf + 0..3 / 16s + 8 + 4hf + 0..3 of this wave's 32
         const u16x8 w = __builtin_bit_cast(u16x8, df);
-        // (128-query block (qt QT) / 128 at st_blk: ds_layout)
+        // (128-query block (qt QT) / 128 at st_blk)
         u16* row = dST + ((int64_t)b * H + h) * st_bh + (int64_t)((qt * QT) >> 7) * st_blk + (int64_t)key * ldst +
                    ((qt * QT) & 127) + 32 * u + 16 * s + 4 * hf;
         *reinterpret_cast<u16x4*>(row) = u16x4{w[0], w[1], w[2], w[3]};
         *reinterpret_cast<u16x4*>(row + 8) = u16x4{w[4], w[5], w[6], w[7]};
       }
-      if constexpr (DMA) {
+      {
         // transposed dO / Q fragments by inline asm, one column block ahead of the MFMAs
         const unsigned kb = lds_addr(buf) + 2u * D * (32u * u + 16u * s);
         s16x4 dl0, dh0, ql0, qh0, dl1, dh1, ql1, qh1;
@@ -1672,28 +1450,15 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_k(
           dk[dt + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, tr_join(ql1, qh1), dk[dt + 1], 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-      } else {
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) {
-        dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, tr_frag<D>(buf + TQ, 32 * u + 16 * s, dt * 32, lane), dv[dt], 0, 0, 0);
-        dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, tr_frag<D>(buf, 32 * u + 16 * s, dt * 32, lane), dk[dt], 0, 0, 0);
-      }
       }
     }
-    if (more) {
-      if constexpr (!DMA) {
-        sq.store(nbuf);
-        sdo.store(nbuf + TQ);
-      }
-      store_aux(nbuf);
-    }
-    if constexpr (DMA) {  // the next tile's DMA landed (MFMAs kept in front of the wait)
-      __builtin_amdgcn_sched_barrier(0);
-      // DS_OUT: the tile's four dS^T stores (two 8-B stores per 16-query slice, after the DMA in
-      // issue order) may stay in flight
-      if constexpr (DS_OUT) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (more) store_aux(nbuf);
+    // the next tile's DMA landed (MFMAs kept in front of the wait)
+    __builtin_amdgcn_sched_barrier(0);
+    // DS_OUT: the tile's four dS^T stores (two 8-B stores per 16-query slice, after the DMA in
+    // issue order) may stay in flight
+    if constexpr (DS_OUT) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
 
@@ -1741,7 +1506,10 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_k(
 // 64-key tiles up to the causal diagonal with K and dS^T tiles staged in LDS, both operands
 // read as transposed fragments (the same k order on both sides). dS^T has LkP =
 // round_up(Lk, 128) rows (keys) of LqP = round_up(Lq, 128) queries (cullavo_attn_bwd_workspace).
-template <int D, bool CAUSAL, bool DMA = false>
+// K and dS^T tiles are staged through registers (StageT): the LDS-DMA and 4-stage ring forms of
+// round 6 moved nothing (130.2 / 129.6 / 130.4 / 131.4 us, profiles/r06/attn/README_r06.txt; the
+// ring kernel lives on in tools/lab/dq_ring.inc).
+template <int D, bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_ds_k(const u16* __restrict__ K, int64_t ldk,
                                                            const u16* __restrict__ dST, int64_t ldst, int64_t st_bh, int64_t st_blk,
                                                            int LkP, u16* __restrict__ dQ, int64_t lddq, int H,
@@ -1774,45 +1542,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_ds_k(const u16* __restrict
   StageT<KT, D> sk;
   StageT<KT, QB> ss;
   const unsigned vok = StageT<KT, D>::lane_off(ldk), vos = StageT<KT, QB>::lane_off(ldst);
-  // DMA (cullavo_attn_set_bwd_stage bit 1): K and dS^T tiles by LDS-DMA into the swizzled
-  // images. Every fragment of a tile is read into registers BEFORE the next tile's DMA is issued:
-  // the transposed reads (builtin, no memory operand) would otherwise each wait for that DMA
-  const int wu = __builtin_amdgcn_readfirstlane(wave);
-  StageDMA<KT, D, 4> dk_;
-  StageDMA<KT, QB, 4> ds_;
-  if constexpr (DMA) {
-    dk_.prep(ldk, wu, lane);
-    ds_.prep(ldst, wu, lane);
-    if (t0 < ntiles) {
-      dk_.issue(Kb, ldk, t0 * KT, Lk, smem, wu);
-      ds_.issue(Sb, ldst, t0 * KT, LkP, smem + TK, wu);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int t = t0; t < ntiles; ++t) {
-      char* bK = smem + ((t - t0) & 1) * BUF;
-      char* bS = bK + TK;
-      frag8 bsf[NS], kf[NS][ND];
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        bsf[s] = tr_frag<QB>(bS, 16 * s, wave * 32, lane);
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) kf[s][dt] = tr_frag<D>(bK, 16 * s, dt * 32, lane);
-      }
-      if (t + 1 < ntiles) {  // the other pair was last read before the previous barrier
-        char* nK = smem + ((t - t0 + 1) & 1) * BUF;
-        dk_.issue(Kb, ldk, (t + 1) * KT, Lk, nK, wu);
-        ds_.issue(Sb, ldst, (t + 1) * KT, LkP, nK + TK, wu);
-      }
-#pragma unroll
-      for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[s][dt], bsf[s], dq[dt], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);  // the MFMAs issue before the wait for the DMA
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-  } else {
   if (t0 < ntiles) {
     sk.load(Kb, ldk, t0 * KT, Lk, vok);
     ss.load(Sb, ldst, t0 * KT, LkP, vos);
@@ -1843,152 +1572,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_ds_k(const u16* __restrict
     }
     __syncthreads();
   }
-  }
-  if (q < Lq) {
-    u16* dQb = dQ + ((int64_t)b * Lq + q) * lddq + (int64_t)h * D;
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        u16x4 w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = f2bf(dq[dt][rr * 4 + j] * scale);
-        *reinterpret_cast<u16x4*>(dQb + dt * 32 + 8 * rr + 4 * hf) = w;
-      }
-  }
-}
-
-// dQ = scale dS K from the stored dS^T, the LDS-DMA ring form (round 6; cullavo_attn_set_bwd_stage
-// bit 2). attn_bwd_dq_ds_k keeps one 64-key tile in flight per workgroup (two per CU): 32 KiB of
-// dS^T per CU against the ~50 KiB that HBM latency x the per-CU share of its bandwidth asks for,
-// so it streams dS^T at ~3 TB/s (118 us per 7B layer, MFMA busy 0.14). Here one workgroup per CU
-// holds NST = 4 stages of (K tile, dS^T tile) in LDS and keeps NST - 1 tiles in flight by
-// LDS-DMA (counted vmcnt: the DMA pieces are the only vector-memory ops in the loop, 2 kPer per
-// tile and wave), with the fragment reads by inline asm (a builtin LDS read would make the
-// compiler wait for every DMA in flight first) tied by counted lgkmcnt. Same tiles, same MFMA
-// order, same epilogue as attn_bwd_dq_ds_k: bitwise the same dQ.
-// (NST, LAB: tools/lab/dq_lab.hip only -- LAB bit 0 skips the fragment reads and MFMAs, bit 1 the
-// K tiles' DMA: timing floors, not results)
-template <int D, bool CAUSAL, int NST = 4, int LAB = 0>
-__global__ __launch_bounds__(256, 1) void attn_bwd_dq_ring_k(const u16* __restrict__ K, int64_t ldk,
-                                                             const u16* __restrict__ dST, int64_t ldst, int64_t st_bh, int64_t st_blk,
-                                                             int LkP, u16* __restrict__ dQ, int64_t lddq, int H,
-                                                             int Lq, int Lk, float scale,
-                                                             const int32_t* __restrict__ kv_start) {
-  static_assert(NST >= 2 && NST <= 4, "2 to 4 stages");
-  constexpr int KT = 64, QB = 128;
-  constexpr int TK = KT * D * 2, TS = KT * QB * 2, BUF = TK + TS;
-  constexpr int NS = KT / 16, ND = D / 32;
-  constexpr unsigned KSTEP = 16 * D * 2, SSTEP = 16 * QB * 2;  // 16 rows: the image swizzle's period
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int nqb = (Lq + QB - 1) / QB;
-  const int lid = xcd_remap(blockIdx.x, gridDim.x);
-  const int qi = lid % nqb, hb = lid / nqb;
-  const int qb = CAUSAL ? (nqb - 1 - qi) : qi;
-  const int h = hb % H, b = hb / H;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hf = lane >> 5;
-  const int q = qb * QB + wave * 32 + (lane & 31);
-  const int kstart = kv_start ? kv_start[b] : 0;
-  const u16* Kb = K + (int64_t)b * Lk * ldk + (int64_t)h * D;
-  const u16* Sb = dST + ((int64_t)b * H + h) * st_bh + qb * st_blk;
-
-  f32x16 dq[ND];
-#pragma unroll
-  for (int i = 0; i < ND; ++i) dq[i] = f32x16(0.f);
-  int kend = Lk;
-  if (CAUSAL) kend = min(Lk, qb * QB + QB);
-  const int ntiles = (kend + KT - 1) / KT;
-  const int t0 = kstart / KT;
-
-  const int wu = __builtin_amdgcn_readfirstlane(wave);
-  StageDMA<KT, D, 4> dk_;
-  StageDMA<KT, QB, 4> ds_;
-  dk_.prep(ldk, wu, lane);
-  ds_.prep(ldst, wu, lane);
-  constexpr int kOps = (LAB & 2 ? 0 : StageDMA<KT, D, 4>::kPer) + StageDMA<KT, QB, 4>::kPer;  // DMA pieces per tile and wave
-  auto issue = [&](int t) {
-    char* bK = smem + ((t - t0) % NST) * BUF;
-    if constexpr (!(LAB & 2)) dk_.issue(Kb, ldk, t * KT, Lk, bK, wu);
-    ds_.issue(Sb, ldst, t * KT, LkP, bK + TK, wu);
-  };
-  // per-lane LDS addresses of tr_frag's two halves (16-key step 0; step s adds s KSTEP / SSTEP)
-  const unsigned sbase = lds_addr(smem);
-  unsigned ko[ND][2], so[2];
-  {
-    const int i = lane & 15, qq = i >> 2, p = i & 3, r0 = 4 * hf + qq;
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt) {
-      const int ch = ((dt * 32 + 16 * ((lane >> 4) & 1)) >> 3) + (p >> 1);
-      ko[dt][0] = sbase + kv_off<D>(r0, ch) + 8 * (p & 1);
-      ko[dt][1] = sbase + kv_off<D>(r0 + 8, ch) + 8 * (p & 1);
-    }
-    const int ch = ((wave * 32 + 16 * ((lane >> 4) & 1)) >> 3) + (p >> 1);
-    so[0] = sbase + TK + kv_off<QB>(r0, ch) + 8 * (p & 1);
-    so[1] = sbase + TK + kv_off<QB>(r0 + 8, ch) + 8 * (p & 1);
-  }
-  // one 16-key step's fragments: dS^T (B operand) and the ND K^T fragments (A operands)
-  struct Grp {
-    s16x4 bl, bh, kl[ND], kh[ND];
-  };
-  // (ko / so as parameters: clang rejects a generic lambda's implicit capture used in asm operands)
-  auto grp_issue = [](auto s_c, Grp& g, unsigned slot, const unsigned (&ko)[ND][2], const unsigned (&so)[2]) {
-    constexpr unsigned S = decltype(s_c)::value;
-    asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4"
-                 : "=&v"(g.bl), "=&v"(g.bh)
-                 : "v"(so[0] + slot), "v"(so[1] + slot), "n"(S * SSTEP)
-                 : "memory");
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-      asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4"
-                   : "=&v"(g.kl[dt]), "=&v"(g.kh[dt])
-                   : "v"(ko[dt][0] + slot), "v"(ko[dt][1] + slot), "n"(S * KSTEP)
-                   : "memory");
-  };
-  auto grp_tie = [](auto cnt_c, Grp& g) {
-    constexpr int CNT = decltype(cnt_c)::value;
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(g.bl), "+v"(g.bh) : "n"(CNT) : "memory");
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt) asm volatile("" : "+v"(g.kl[dt]), "+v"(g.kh[dt]));
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto grp_mfma = [&](const Grp& g) {
-    const frag8 bs = tr_join(g.bl, g.bh);
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_join(g.kl[dt], g.kh[dt]), bs, dq[dt], 0, 0, 0);
-  };
-  using C0 = std::integral_constant<int, 0>;
-  using CG = std::integral_constant<int, 2 * (ND + 1)>;  // one group's reads
-  static_assert(NS == 4 && 2 * (ND + 1) <= 15, "lgkmcnt counts one group in flight");
-
-  for (int j = 0; j < NST - 1; ++j)
-    if (t0 + j < ntiles) issue(t0 + j);
-  for (int t = t0; t < ntiles; ++t) {
-    // tile t landed: the tiles after it that are already issued may stay in flight
-    const int after = min(NST - 2, ntiles - 1 - t);
-    if (after >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kOps) : "memory");
-    else if (after == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kOps) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // every wave's pieces of tile t are in, and every wave is done reading the slot refilled next
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (t + NST - 1 < ntiles) issue(t + NST - 1);
-    if constexpr (LAB & 1) continue;
-    const unsigned slot = (unsigned)(((t - t0) % NST) * BUF);
-    Grp ga, gb;
-    grp_issue(std::integral_constant<unsigned, 0>{}, ga, slot, ko, so);
-    grp_issue(std::integral_constant<unsigned, 1>{}, gb, slot, ko, so);
-    grp_tie(CG{}, ga);
-    grp_mfma(ga);
-    grp_issue(std::integral_constant<unsigned, 2>{}, ga, slot, ko, so);
-    grp_tie(CG{}, gb);
-    grp_mfma(gb);
-    grp_issue(std::integral_constant<unsigned, 3>{}, gb, slot, ko, so);
-    grp_tie(CG{}, ga);
-    grp_mfma(ga);
-    grp_tie(C0{}, gb);
-    grp_mfma(gb);
-  }
   if (q < Lq) {
     u16* dQb = dQ + ((int64_t)b * Lq + q) * lddq + (int64_t)h * D;
 #pragma unroll
@@ -2018,152 +1601,82 @@ int fwd_launch(const u16* q, int64_t ldq, const u16* k, int64_t ldk, const u16* 
   const int smem = 4 * 64 * D * 2;
   static bool once = false;
   if (!once) {
-    set_smem(attn_fwd_k<D, CAUSAL, 0>, smem);
-    set_smem(attn_fwd_k<D, CAUSAL, 1>, smem);
-    set_smem(attn_fwd_k<D, CAUSAL, 2>, smem);
-    set_smem(attn_fwd_k<D, CAUSAL, 2, 1>, smem);
-    set_smem(attn_fwd_k<D, CAUSAL, 4>, smem);
-    set_smem(attn_fwd_k<D, CAUSAL, 5>, smem);
-    set_smem(attn_fwd_k<D, CAUSAL, 6>, smem);
+    set_smem(attn_fwd_k<D, CAUSAL>, smem);
     set_smem(attn_fwd_pipe_k<D, CAUSAL>, smem);
     once = true;
   }
   const unsigned grid = (unsigned)(cdiv(Lq, 128) * H * B);
-  const int stage = g_fwd_stage >= 0 ? g_fwd_stage : 7;
-  if (stage == 7)
-    attn_fwd_pipe_k<D, CAUSAL><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, Lq, Lk, scale, ks);
-  else if (stage == 6)
-    attn_fwd_k<D, CAUSAL, 6><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, Lq, Lk, scale, ks);
-  else if (stage == 5)
-    attn_fwd_k<D, CAUSAL, 5><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, Lq, Lk, scale, ks);
-  else if (stage == 4)
-    attn_fwd_k<D, CAUSAL, 4><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, Lq, Lk, scale, ks);
-  else if (stage == 3)
-    attn_fwd_k<D, CAUSAL, 2, 1><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, Lq, Lk, scale, ks);
-  else if (stage == 2)
-    attn_fwd_k<D, CAUSAL, 2><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, Lq, Lk, scale, ks);
-  else if (stage == 1)
-    attn_fwd_k<D, CAUSAL, 1><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, Lq, Lk, scale, ks);
+  if (g_fwd_stage == 4)
+    attn_fwd_k<D, CAUSAL><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, Lq, Lk, scale, ks);
   else
-    attn_fwd_k<D, CAUSAL, 0><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, Lq, Lk, scale, ks);
+    attn_fwd_pipe_k<D, CAUSAL><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, Lq, Lk, scale, ks);
   return cullavo_check_launch("attn_fwd");
 }
 
-template <int D, bool CAUSAL, int QT, int KT>
+// backward mode (cullavo_attn_set_bwd_tiles):
+//   0 = the 4-wave kernels, 32-row dK/dV tiles and 32-key dQ tiles (the plain pair);
+//   2 = as 0 with 64-key dQ tiles, bitwise equal to 0;
+//   4 = the 8-wave dK/dV kernel + the 4-wave dQ kernel with 32-key tiles (the recompute path; also
+//       what mode 7 runs when no dS^T workspace is given);
+//   7 = the 8-wave dK/dV kernel storing dS^T + dQ from it (workspace: B*H*LkP*LqP bf16);
+//  -1 = per head dim, see bwd_mode.
+// The 64-row dK/dV tiles (modes 1, 3) lost the tile sweep on both head dims and left with ABI 6.
+int g_bwd_tiles = -1;
+
+// delta, then the mode's dK/dV kernel, then its dQ kernel (ds: the dS^T workspace of mode 7)
+template <int D, bool CAUSAL>
 int bwd_launch(const u16* q, int64_t ldq, const u16* k, int64_t ldk, const u16* v, int64_t ldv, const u16* o,
                int64_t ldo, const u16* dout, int64_t lddo, const float* lse, float* delta, u16* dq, int64_t lddq,
                u16* dk, int64_t lddk, u16* dv, int64_t lddv, int B, int H, int Lq, int Lk, float scale,
-               const int32_t* ks, hipStream_t s) {
-  const int64_t rows = (int64_t)B * Lq * H;
-  attn_delta_k<D><<<(unsigned)cdiv(rows * (D / 8), 256), 256, 0, s>>>(o, ldo, dout, lddo, delta, B, H, Lq);
-  const int smem_a = 2 * (2 * QT * D * 2 + 2 * QT * 4);
-  const int smem_b = 4 * KT * D * 2;
-  static bool once = false;
-  if (!once) {
-    set_smem(attn_bwd_dkdv_k<D, CAUSAL, QT>, smem_a);
-    set_smem(attn_bwd_dq_k<D, CAUSAL, KT>, smem_b);
-    once = true;
-  }
-  const unsigned ga = (unsigned)(cdiv(Lk, 128) * H * B);
-  attn_bwd_dkdv_k<D, CAUSAL, QT><<<ga, 256, smem_a, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk,
-                                                      dv, lddv, H, Lq, Lk, scale, ks);
-  const unsigned gb = (unsigned)(cdiv(Lq, 128) * H * B);
-  attn_bwd_dq_k<D, CAUSAL, KT><<<gb, 256, smem_b, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq, lddq, H,
-                                                    Lq, Lk, scale, ks);
-  return cullavo_check_launch("attn_bwd");
-}
-
-// mode 4: the 8-wave dK/dV kernel + the 4-wave dQ kernel with 32-key tiles (the recompute path
-// when no dS^T workspace is given; the 8-wave dQ kernel, mode 5, measured slower: 284 vs 251 us per
-// 7B layer, and was removed in round 5)
-template <int D, bool CAUSAL>
-int bwd8_launch(const u16* q, int64_t ldq, const u16* k, int64_t ldk, const u16* v, int64_t ldv, const u16* o,
-                int64_t ldo, const u16* dout, int64_t lddo, const float* lse, float* delta, u16* dq, int64_t lddq,
-                u16* dk, int64_t lddk, u16* dv, int64_t lddv, int B, int H, int Lq, int Lk, float scale,
-                const int32_t* ks, hipStream_t s) {
-  const int64_t rows = (int64_t)B * Lq * H;
-  attn_delta_k<D><<<(unsigned)cdiv(rows * (D / 8), 256), 256, 0, s>>>(o, ldo, dout, lddo, delta, B, H, Lq);
-  // dK/dV: K, V images (2 x 128 x D) + 2 x [Q | dO | lse | delta] tiles of 64 rows; the pair
+               const int32_t* ks, int mode, u16* ds, hipStream_t s) {
+  // 4-wave dK/dV: 2 x [Q | dO | lse | delta] tiles of 32 rows
+  const int smem_a4 = 2 * (2 * 32 * D * 2 + 2 * 32 * 4);
+  // 8-wave dK/dV: K, V images (2 x 128 x D) + 2 x [Q | dO | lse | delta] tiles of 64 rows; the pair
   // reduction reuses the front 2 x 4 x 32 x D f32 of it
-  const int smem_a = std::max(2 * 128 * D * 2 + 2 * (2 * 64 * D * 2 + 2 * 64 * 4), 2 * 4 * 32 * D * 4);
-  const int smem_b = 4 * 32 * D * 2;
+  const int smem_a8 = std::max(2 * 128 * D * 2 + 2 * (2 * 64 * D * 2 + 2 * 64 * 4), 2 * 4 * 32 * D * 4);
+  const int smem_q32 = 4 * 32 * D * 2, smem_q64 = 4 * 64 * D * 2;  // dQ: 2 x [K | V] tiles
+  const int smem_qds = 2 * (64 * D * 2 + 64 * 128 * 2);            // dQ from dS^T: 2 x [K | dS^T] tiles
   static bool once = false;
   if (!once) {
-    set_smem(attn_bwd_dkdv8_k<D, CAUSAL>, smem_a);
-    set_smem(attn_bwd_dkdv8_k<D, CAUSAL, false, true>, smem_a);
-    set_smem(attn_bwd_dq_k<D, CAUSAL, 32>, smem_b);
+    set_smem(attn_bwd_dkdv_k<D, CAUSAL>, smem_a4);
+    set_smem(attn_bwd_dkdv8_k<D, CAUSAL, false>, smem_a8);
+    set_smem(attn_bwd_dkdv8_k<D, CAUSAL, true>, smem_a8);
+    set_smem(attn_bwd_dq_k<D, CAUSAL, 32>, smem_q32);
+    set_smem(attn_bwd_dq_k<D, CAUSAL, 64>, smem_q64);
+    set_smem(attn_bwd_dq_ds_k<D, CAUSAL>, smem_qds);
     once = true;
   }
-  if (g_bwd_stage & 1)
-    attn_bwd_dkdv8_k<D, CAUSAL, false, true><<<(unsigned)(cdiv(Lk, 128) * H * B), 512, smem_a, s>>>(
-        q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk, dv, lddv, H, Lq, Lk, scale, ks, nullptr, 0, 0, 0);
-  else
-    attn_bwd_dkdv8_k<D, CAUSAL><<<(unsigned)(cdiv(Lk, 128) * H * B), 512, smem_a, s>>>(
-        q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk, dv, lddv, H, Lq, Lk, scale, ks, nullptr, 0, 0, 0);
-  attn_bwd_dq_k<D, CAUSAL, 32><<<(unsigned)(cdiv(Lq, 128) * H * B), 256, smem_b, s>>>(
-      q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq, lddq, H, Lq, Lk, scale, ks);
-  return cullavo_check_launch("attn_bwd");
-}
-
-// mode 7: the 8-wave dK/dV kernel storing dS^T + dQ from it (workspace: B*H*LkP*LqP bf16)
-template <int D, bool CAUSAL>
-int bwd_ds_launch(const u16* q, int64_t ldq, const u16* k, int64_t ldk, const u16* v, int64_t ldv, const u16* o,
-                  int64_t ldo, const u16* dout, int64_t lddo, const float* lse, float* delta, u16* dq, int64_t lddq,
-                  u16* dk, int64_t lddk, u16* dv, int64_t lddv, int B, int H, int Lq, int Lk, float scale,
-                  const int32_t* ks, u16* ds, hipStream_t s) {
   const int64_t rows = (int64_t)B * Lq * H;
   attn_delta_k<D><<<(unsigned)cdiv(rows * (D / 8), 256), 256, 0, s>>>(o, ldo, dout, lddo, delta, B, H, Lq);
-  const int smem_a = std::max(2 * 128 * D * 2 + 2 * (2 * 64 * D * 2 + 2 * 64 * 4), 2 * 4 * 32 * D * 4);
-  const int smem_b = 2 * (64 * D * 2 + 64 * 128 * 2);
-  const int smem_r = 4 * (64 * D * 2 + 64 * 128 * 2);  // attn_bwd_dq_ring_k's 4 stages (128 KiB at D = 128)
-  static bool once = false;
-  if (!once) {
-    set_smem(attn_bwd_dkdv8_k<D, CAUSAL, true>, smem_a);
-    set_smem(attn_bwd_dkdv8_k<D, CAUSAL, true, true>, smem_a);
-    set_smem(attn_bwd_dq_ds_k<D, CAUSAL>, smem_b);
-    set_smem(attn_bwd_dq_ds_k<D, CAUSAL, true>, smem_b);
-    if constexpr (D == 128) set_smem(attn_bwd_dq_ring_k<D, CAUSAL>, smem_r);
-    once = true;
-  }
+  const unsigned gk = (unsigned)(cdiv(Lk, 128) * H * B), gq = (unsigned)(cdiv(Lq, 128) * H * B);
+  // the dS^T workspace is row-major: LkP key rows of LqP queries, 128-query block qb at column 128 qb
   const int64_t LkP = ds_rows(Lk), LqP = ds_cols(Lq);
-  // dS^T layout (ds_layout): row stride and 128-query block stride
-  const bool blk = (g_bwd_stage & 8) != 0;
-  const int64_t ldst = blk ? 128 : LqP, st_blk = blk ? LkP * 128 : 128;
-  if (g_bwd_stage & 1)
-    attn_bwd_dkdv8_k<D, CAUSAL, true, true><<<(unsigned)(cdiv(Lk, 128) * H * B), 512, smem_a, s>>>(
-        q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk, dv, lddv, H, Lq, Lk, scale, ks, ds, ldst, LkP * LqP, st_blk);
+  if (mode == 7)
+    attn_bwd_dkdv8_k<D, CAUSAL, true><<<gk, 512, smem_a8, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk,
+                                                             dv, lddv, H, Lq, Lk, scale, ks, ds, LqP, LkP * LqP, 128);
+  else if (mode == 4)
+    attn_bwd_dkdv8_k<D, CAUSAL, false><<<gk, 512, smem_a8, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk,
+                                                              dv, lddv, H, Lq, Lk, scale, ks, nullptr, 0, 0, 0);
   else
-    attn_bwd_dkdv8_k<D, CAUSAL, true><<<(unsigned)(cdiv(Lk, 128) * H * B), 512, smem_a, s>>>(
-        q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk, dv, lddv, H, Lq, Lk, scale, ks, ds, ldst, LkP * LqP, st_blk);
-  if (D == 128 && (g_bwd_stage & 4))
-    attn_bwd_dq_ring_k<D, CAUSAL><<<(unsigned)(cdiv(Lq, 128) * H * B), 256, smem_r, s>>>(
-        k, ldk, ds, ldst, LkP * LqP, st_blk, (int)LkP, dq, lddq, H, Lq, Lk, scale, ks);
-  else if (g_bwd_stage & 2)
-    attn_bwd_dq_ds_k<D, CAUSAL, true><<<(unsigned)(cdiv(Lq, 128) * H * B), 256, smem_b, s>>>(
-        k, ldk, ds, ldst, LkP * LqP, st_blk, (int)LkP, dq, lddq, H, Lq, Lk, scale, ks);
+    attn_bwd_dkdv_k<D, CAUSAL><<<gk, 256, smem_a4, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk, dv,
+                                                      lddv, H, Lq, Lk, scale, ks);
+  if (mode == 7)
+    attn_bwd_dq_ds_k<D, CAUSAL><<<gq, 256, smem_qds, s>>>(k, ldk, ds, LqP, LkP * LqP, 128, (int)LkP, dq, lddq, H, Lq, Lk,
+                                                        scale, ks);
+  else if (mode == 2)
+    attn_bwd_dq_k<D, CAUSAL, 64><<<gq, 256, smem_q64, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq, lddq, H,
+                                                         Lq, Lk, scale, ks);
   else
-    attn_bwd_dq_ds_k<D, CAUSAL><<<(unsigned)(cdiv(Lq, 128) * H * B), 256, smem_b, s>>>(
-        k, ldk, ds, ldst, LkP * LqP, st_blk, (int)LkP, dq, lddq, H, Lq, Lk, scale, ks);
+    attn_bwd_dq_k<D, CAUSAL, 32><<<gq, 256, smem_q32, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq, lddq, H,
+                                                         Lq, Lk, scale, ks);
   return cullavo_check_launch("attn_bwd");
 }
-
-
-// backward tile shape (cullavo_attn_set_bwd_tiles): bit 0 -> 64 query rows per dK/dV
-// barrier, bit 1 -> 64 keys per dQ barrier (else 32); -1 = per head dim, from the MI355X
-// sweep in tools/attn_bench.py: D=128 causal 64/32 (730 vs 746 us), D=64 32/64 (636 vs 646 us)
-int g_bwd_tiles = -1;
 
 }  // namespace
 
-extern "C" int cullavo_attn_set_stage(int buffer_loads) {
+extern "C" int cullavo_attn_set_stage(int stage) {
   const int prev = g_fwd_stage;
-  if (buffer_loads >= -1 && buffer_loads <= 7) g_fwd_stage = buffer_loads;
-  return prev;
-}
-
-extern "C" int cullavo_attn_set_bwd_stage(int mode) {
-  const int prev = g_bwd_stage;
-  if (mode >= 0 && mode <= 15) g_bwd_stage = mode;
+  if (stage == -1 || stage == 4 || stage == 7) g_fwd_stage = stage;
   return prev;
 }
 
@@ -2177,7 +1690,7 @@ extern "C" int cullavo_attn_set_rescale(float threshold, float* previous) {
 
 extern "C" int cullavo_attn_set_bwd_tiles(int mode) {
   const int prev = g_bwd_tiles;
-  if ((mode >= -1 && mode <= 4) || mode == 7) g_bwd_tiles = mode;
+  if (mode == -1 || mode == 0 || mode == 2 || mode == 4 || mode == 7) g_bwd_tiles = mode;
   return prev;
 }
 
@@ -2206,7 +1719,9 @@ extern "C" int cullavo_attn_fwd(const void* q, int64_t ldq, const void* k, int64
 }
 
 // default: D=128 (the LM) mode 7 -- in the 7B shape 532 us per layer against 667 for mode 4
-// (tools/attn_bench.py), the dQ kernel no longer recomputes S and dP; D=64 (the ViT) mode 2
+// (tools/attn_bench.py), the dQ kernel no longer recomputes S and dP; D=64 (the ViT) mode 2 (647
+// vs 797 us for mode 4 at B=64, T=577, H=16: there the 4-wave kernels already hold K/V in registers
+// at < 256 VGPRs and the 8-wave LDS re-reads cost more than the second wave hides)
 static int bwd_mode(int D) { return g_bwd_tiles >= 0 ? g_bwd_tiles : (D == 128 ? 7 : 2); }
 
 extern "C" size_t cullavo_attn_bwd_workspace(int B, int H, int Lq, int Lk, int D, int dtype) {
@@ -2244,35 +1759,18 @@ extern "C" int cullavo_attn_bwd_ws(const void* q, int64_t ldq, const void* k, in
                                     lddv, B, H, Lq, Lk, D, scale, causal, kv_start, dtype, s);
   const u16 *Q = (const u16*)q, *K = (const u16*)k, *V = (const u16*)v, *O = (const u16*)o, *dO = (const u16*)dout;
   u16 *dQ = (u16*)dq, *dK = (u16*)dk, *dV = (u16*)dv;
-#define BWD4(DD, CC, QQ, KK) bwd_launch<DD, CC, QQ, KK>(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, delta, dQ, lddq, dK, lddk, dV, lddv, B, H, Lq, Lk, scale, kv_start, s)
-  // default: D=128 (the LM) the 8-wave dK/dV kernel + the 4-wave 32-key dQ kernel (mode 4;
-  // in the 7B step 356 + 251 us per layer vs 467 + 251 for the 4-wave pair; the 8-wave dQ
-  // kernel, mode 5, took 284 us);
-  // D=64 (the ViT) the 4-wave kernels with 32-row dK/dV and 64-key dQ tiles (647 vs 797 us at
-  // B=64, T=577, H=16): there the 4-wave kernels already hold K/V in registers at < 256
-  // VGPRs and the 8-wave LDS re-reads cost more than the second wave hides (tools/attn_bench.py)
+  // mode 7 needs its dS^T workspace; without one the recompute path runs (mode 4: the same dK / dV
+  // kernel without the dS^T stores, and the 4-wave dQ kernel)
   int mode = bwd_mode(D);
-  if (mode == 7) {
-    if (workspace != nullptr && workspace_bytes >= cullavo_attn_bwd_workspace(B, H, Lq, Lk, D, dtype)) {
-      u16* ds = (u16*)workspace;
-#define BDS(DD, CC) bwd_ds_launch<DD, CC>(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, delta, dQ, lddq, dK, lddk, dV, lddv, B, H, Lq, Lk, scale, kv_start, ds, s)
-      if (D == 128) return causal ? BDS(128, true) : BDS(128, false);
-      return causal ? BDS(64, true) : BDS(64, false);
-#undef BDS
-    }
-    mode = 4;  // no dS workspace: the recompute path (same dK / dV kernel)
-  }
-  if (mode == 4) {
-#define B8(DD, CC) bwd8_launch<DD, CC>(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, delta, dQ, lddq, dK, lddk, dV, lddv, B, H, Lq, Lk, scale, kv_start, s)
-    if (D == 128) return causal ? B8(128, true) : B8(128, false);
-    return causal ? B8(64, true) : B8(64, false);
-#undef B8
-  }
-  const int tiles = mode;
-#define BWD(DD, CC) (tiles == 3 ? BWD4(DD, CC, 64, 64) : tiles == 2 ? BWD4(DD, CC, 32, 64) \
-                     : tiles == 1 ? BWD4(DD, CC, 64, 32) : BWD4(DD, CC, 32, 32))
-  if (D == 128) return causal ? BWD(128, true) : BWD(128, false);
-  return causal ? BWD(64, true) : BWD(64, false);
-#undef BWD
-#undef BWD4
+  u16* ds = (u16*)workspace;
+  if (mode == 7 && (ds == nullptr || workspace_bytes < cullavo_attn_bwd_workspace(B, H, Lq, Lk, D, dtype))) mode = 4;
+  auto run = [&](auto d_c, auto causal_c) {
+    return bwd_launch<decltype(d_c)::value, decltype(causal_c)::value>(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse,
+                                                                       delta, dQ, lddq, dK, lddk, dV, lddv, B, H, Lq,
+                                                                       Lk, scale, kv_start, mode, ds, s);
+  };
+  using D128 = std::integral_constant<int, 128>;
+  using D64 = std::integral_constant<int, 64>;
+  if (D == 128) return causal ? run(D128{}, std::true_type{}) : run(D128{}, std::false_type{});
+  return causal ? run(D64{}, std::true_type{}) : run(D64{}, std::false_type{});
 }

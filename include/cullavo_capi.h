@@ -52,9 +52,11 @@ extern "C" {
    out_dtype, cullavo_vision_embed_ln dtype, cullavo_gemm_desc f32_operands; 4: the tuning switches
    of the measured-slower GEMM variants removed with them: cullavo_gemm_set_streamk,
    cullavo_gemm_set_prefetch, cullavo_gemm_set_loaders; 5: the NF4 entry points cullavo_nf4_quantize,
-   cullavo_nf4_dequantize, cullavo_nf4_decode_linear added). A consumer built against this header
-   checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
-#define CULLAVO_ABI_VERSION 5
+   cullavo_nf4_dequantize, cullavo_nf4_decode_linear added; 6: the switches of the measured-slower
+   attention and GEMV variants removed with them: the attention backward's staging setter, the
+   decode GEMV's non-temporal-load setter, and the retired values of cullavo_attn_set_stage /
+   cullavo_attn_set_bwd_tiles). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
+#define CULLAVO_ABI_VERSION 6
 
 int cullavo_abi_version(void);
 const char* cullavo_last_error(void);
@@ -197,10 +199,6 @@ int cullavo_gemm_set_epilogue(int lds_staged);
    or the operand is stored [K][rows], layout 1; the default); 0 = offsets recomputed per
    K-tile. Same results either way. Returns the previous setting. */
 int cullavo_gemm_set_dma(int precomputed);
-/* Tuning/A-B switch for the decode product (plan 14, cullavo_decode_linear): 1 = the weight
-   fragments are read with non-temporal loads (each weight byte is read once per token step), 0 =
-   default cache policy. Same results either way. Returns the previous setting. */
-int cullavo_gemv_set_nt(int on);
 /* The kernel shape cullavo_gemm will use for this problem (return value, as above) and its
  * number of workgroups (*grid, nullable) — lets profilers match dispatches to GEMM calls.
  * 9 = the 8-wave 256x256 kernel split over K (a grid of at most half the CUs with >= 32
@@ -310,39 +308,24 @@ int cullavo_attn_bwd_ws(const void* q, int64_t ldq, const void* k, int64_t ldk, 
                         size_t workspace_bytes, void* stream);
 /* bytes of workspace cullavo_attn_bwd_ws uses for this problem in the current mode (0: none) */
 size_t cullavo_attn_bwd_workspace(int B, int H, int Lq, int Lk, int D, int dtype);
-/* Tuning/A-B switch for cullavo_attn_bwd: 4 = the 8-wave dK/dV kernel (two waves per SIMD;
-   waves w and w+4 split each query tile and add their partial sums once, in a fixed order)
-   with the 4-wave 32-key dQ kernel; 0-3 = the 4-wave kernels; 7 = mode 4's dK/dV
-   kernel storing dS^T + dQ from it (needs the cullavo_attn_bwd_ws workspace); -1 (the default) = 7 for D=128 (4 through cullavo_attn_bwd, which has no workspace), 2 for
-   D=64 (measured per head dim).
-   In 0-3 with bit 0 = 64 query rows per dK/dV barrier, bit 1 = 64
-   keys per dQ barrier (else 32) -- results bitwise identical across 0-3 (same products summed
-   in the same order). Modes 5, 6 and 8 (measured slower: both kernels 8-wave, 64 keys per wave,
-   the software-pipelined mode-7 pair; profiles/r02/attn/, profiles/r04/attn/) were removed in
-   round 5. Other values leave the mode unchanged. Returns the previous mode. */
+/* Kernel choice of cullavo_attn_bwd, accepted values -1, 0, 2, 4, 7:
+   0 = the 4-wave kernels with 32-row dK/dV tiles and 32-key dQ tiles (the plain pair);
+   2 = as 0 with 64-key dQ tiles, bitwise equal to 0 (same products summed in the same order);
+   4 = the 8-wave dK/dV kernel (two waves per SIMD; waves w and w+4 split each query tile and add
+       their partial sums once, in a fixed order) with the 4-wave 32-key dQ kernel;
+   7 = mode 4's dK/dV kernel storing dS^T + dQ from it (needs the cullavo_attn_bwd_ws workspace;
+       without one mode 4 runs);
+   -1 (the default) = 7 for D=128, 2 for D=64 (measured per head dim).
+   Modes 1 and 3 (64-row dK/dV tiles, slower on both head dims) were removed with ABI 6, modes 5, 6
+   and 8 in round 5. Any other value leaves the mode unchanged. Returns the previous mode. */
 int cullavo_attn_set_bwd_tiles(int mode);
-/* A/B switch for the attention forward's K/V tile staging: 2 = 16-B buffer loads
-   through a per-tile scalar descriptor (one loop-invariant lane offset, rows past the sequence
-   end zero-filled by the range check), 1 = buffer loads with per-chunk offsets and range selects,
-   0 = pointer loads behind a per-chunk bounds branch, 3 = mode 2 with the two MFMA blocks of a
-   K/V tile at raised wave priority (s_setprio; A/B experiment), 4 = K/V tiles by
-   LDS-DMA (buffer_load ... lds) straight into the swizzled LDS image (no staging registers, no
-   ds_write), 5 = mode 4 with the K and V^T fragment reads as inline-asm groups of 4 under
-   counted lgkmcnt waits (the next group in flight while the current one's MFMAs issue), 7 = the
-   software-pipelined kernel (tile t's softmax in the issue gaps of tile t+1's S MFMAs, K / V in
-   rings of their own), -1 (the default) = 7.
-   Results are identical. Other
-   values leave the setting; returns the previous setting. Not thread-safe. */
-int cullavo_attn_set_stage(int buffer_loads);
-/* A/B switch for the backward's tile staging, three bits: bit 0 = the 8-wave dK/dV kernel's
-   (modes 4, 5, 7) Q / dO tiles, bit 1 = the mode-7 dQ kernel's K / dS^T tiles by LDS-DMA
-   straight into the swizzled image (else through registers and ds_write); the default is 1
-   (round 5: with LDS-DMA staging the dK/dV kernel's fragment reads are inline asm, one step ahead
-   of the MFMAs). Bit 2 (round 6, head dim 128): the mode-7 dQ kernel as a 4-stage LDS-DMA ring,
-   one workgroup per CU with three 64-key tiles in flight (takes precedence over bit 1). Bit 3
-   (round 6): the dS^T workspace blocked by 128-query column blocks (a dQ tile is one contiguous
-   16 KiB run instead of 64 rows of 256 B). Results are identical. Other values leave the setting; returns the previous one. */
-int cullavo_attn_set_bwd_stage(int mode);
+/* Kernel choice of cullavo_attn_fwd, accepted values -1, 4, 7: 4 = the plain kernel (K/V tiles by
+   LDS-DMA straight into the swizzled LDS image, a tile's S, softmax and P V in program order);
+   7 = the software-pipelined kernel (tile t's softmax in the issue gaps of tile t+1's S MFMAs,
+   K / V in rings of their own); -1 (the default) = 7. Results are bitwise identical. The
+   register-staged forms 0-3 and the inline-asm form 5 were removed with ABI 6. Any other value
+   leaves the setting; returns the previous setting. Not thread-safe. */
+int cullavo_attn_set_stage(int stage);
 /* Attention forward's deferred rescale (guide T13): the running row max and the O / l rescale
    move only on K/V tiles where some row's max grew by more than `threshold` (log2 units, in
    [0, 16]; default 8: softmax weights stay <= 2^8 against the stale max, LSE exact). 0 = rescale

@@ -1,6 +1,6 @@
 """Static check of the built library's machine code (no GPU): the kernels that issue LDS reads as
-inline asm and wait for them later with a counted `s_waitcnt lgkmcnt(N)` (attention forward stages
-5 / 7, the LDS-DMA dK/dV backward kernel) are only
+inline asm and wait for them later with a counted `s_waitcnt lgkmcnt(N)` (the pipelined attention
+forward, the LDS-DMA dK/dV backward kernel) are only
 correct if nothing reads or overwrites a read's destination registers before that wait. The
 compiler does not know the data lands late: a spill store, a register copy or a branch placed
 between the read and its wait would use stale values (round 4: a spill store of in-flight
@@ -20,12 +20,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "causal-unified-language-vision_amd", "libcullavo_hip.so")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 # kernels whose LDS reads are inline asm with deferred counted waits
-ASM_READ_KERNELS = ("attn_fwd_pipe_k", "attn_fwd_kILi128ELb1ELi5E", "attn_fwd_kILi64ELb0ELi5E",
-                    # round 5: the LDS-DMA dK/dV kernel's fragment reads (DMA = true instantiations)
-                    "attn_bwd_dkdv8_kILi128ELb1ELb1ELb1E", "attn_bwd_dkdv8_kILi128ELb1ELb0ELb1E",
-                    "attn_bwd_dkdv8_kILi128ELb0ELb1ELb1E", "attn_bwd_dkdv8_kILi128ELb0ELb0ELb1E",
-                    "attn_bwd_dkdv8_kILi64ELb1ELb1ELb1E", "attn_bwd_dkdv8_kILi64ELb0ELb1ELb1E",
-                    "attn_bwd_dkdv8_kILi64ELb1ELb0ELb1E", "attn_bwd_dkdv8_kILi64ELb0ELb0ELb1E")
+# (mangled <D, CAUSAL> of attn_fwd_pipe_k, <D, CAUSAL, DS_OUT> of attn_bwd_dkdv8_k, template list closed)
+ASM_READ_KERNELS = ("attn_fwd_pipe_kILi128ELb1EE", "attn_fwd_pipe_kILi128ELb0EE",
+                    "attn_fwd_pipe_kILi64ELb1EE", "attn_fwd_pipe_kILi64ELb0EE",
+                    # round 5: the LDS-DMA dK/dV kernel's fragment reads
+                    "attn_bwd_dkdv8_kILi128ELb1ELb1EE", "attn_bwd_dkdv8_kILi128ELb1ELb0EE",
+                    "attn_bwd_dkdv8_kILi128ELb0ELb1EE", "attn_bwd_dkdv8_kILi128ELb0ELb0EE",
+                    "attn_bwd_dkdv8_kILi64ELb1ELb1EE", "attn_bwd_dkdv8_kILi64ELb0ELb1EE",
+                    "attn_bwd_dkdv8_kILi64ELb1ELb0EE", "attn_bwd_dkdv8_kILi64ELb0ELb0EE")
+
+
+def _listed(kernels, names):
+    """the disassembled kernels matching the listed names; every listed name must match one (a
+    renamed kernel or a changed template list must not silently empty the check)"""
+    missing = [k for k in names if not any(k in n for n in kernels)]
+    assert not missing, f"listed kernels not in the disassembly: {missing}"
+    return [n for n in kernels if any(k in n for k in names)]
 
 
 def _regs(spec):
@@ -102,11 +112,11 @@ def _early_uses(body, allow_branch=False):
     return bad
 
 
-# the dK/dV kernels that store dS^T while the next tile's LDS-DMA is in flight (DS_OUT = DMA = true):
+# the dK/dV kernels that store dS^T while the next tile's LDS-DMA is in flight (DS_OUT = true):
 # their loop ends with a hand-counted `s_waitcnt vmcnt(4)` that lets exactly the tile's four dS^T stores
-# stay outstanding (attention.hip, the DMA branch at the end of the tile loop)
-DS_OUT_DMA_KERNELS = ("attn_bwd_dkdv8_kILi128ELb1ELb1ELb1E", "attn_bwd_dkdv8_kILi128ELb0ELb1ELb1E",
-                      "attn_bwd_dkdv8_kILi64ELb1ELb1ELb1E", "attn_bwd_dkdv8_kILi64ELb0ELb1ELb1E")
+# stay outstanding (attention.hip, the end of the tile loop)
+DS_OUT_DMA_KERNELS = ("attn_bwd_dkdv8_kILi128ELb1ELb1EE", "attn_bwd_dkdv8_kILi128ELb0ELb1EE",
+                      "attn_bwd_dkdv8_kILi64ELb1ELb1EE", "attn_bwd_dkdv8_kILi64ELb0ELb1EE")
 
 
 def _counted_vmcnt_problems(body, n=4):
@@ -163,7 +173,7 @@ def test_dkdv_dsout_counted_vmcnt_leaves_only_the_stores():
     """the LDS-DMA dK/dV kernel's `vmcnt(4)` assumes the four dS^T stores are the only
     vector-memory ops issued after the next tile's DMA and aux loads; checked on the built code."""
     kernels = _kernels()
-    checked = [n for n in kernels if any(k in n for k in DS_OUT_DMA_KERNELS)]
+    checked = _listed(kernels, DS_OUT_DMA_KERNELS)
     assert len(checked) == len(DS_OUT_DMA_KERNELS), checked
     problems = {}
     for n in checked:
@@ -178,8 +188,8 @@ def test_dkdv_dsout_counted_vmcnt_leaves_only_the_stores():
 @pytest.mark.skipif(not (os.path.exists(LIB) and os.path.exists(OBJDUMP)), reason="library or llvm-objdump missing")
 def test_inline_asm_lds_reads_not_used_before_their_wait():
     kernels = _kernels()
-    checked = [n for n in kernels if any(k in n for k in ASM_READ_KERNELS)]
-    assert any("attn_fwd_pipe_k" in n for n in checked) and any("attn_fwd_kILi128ELb1ELi5E" in n for n in checked)
+    checked = _listed(kernels, ASM_READ_KERNELS)
+    assert len(checked) == len(ASM_READ_KERNELS), checked
     problems = {}
     for n in checked:
         bad = _early_uses([ins for _, ins in kernels[n]], allow_branch=False)

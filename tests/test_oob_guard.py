@@ -103,7 +103,8 @@ def _attn_ref(q, k, v, do, B, H, L, D, causal):
 def test_attention_rows_past_end_next_to_nan(B, H, L, D, causal):
     """q|k|v as column blocks of a fused [T, 3*H*D] buffer followed by NaN rows, dO and O
     followed by NaN rows; L not a multiple of 64, so the last tile of the last sequence reaches
-    past the tensor. Every forward staging mode and every backward tile / staging mode."""
+    past the tensor. Both forward kernels and every 8-wave backward mode (plus the 4-wave pair at
+    D = 64)."""
     from cullavo_amd import _lib, ops
     Lb = _lib.lib()
     hd = H * D
@@ -117,37 +118,26 @@ def test_attention_rows_past_end_next_to_nan(B, H, L, D, causal):
     outs = {}
     prev = Lb.cullavo_attn_set_stage(4)
     try:
-        for st in (0, 1, 2, 4, 5, 7):
+        for st in (4, 7):
             Lb.cullavo_attn_set_stage(st)
             o, lse = ops.attn_fwd(qd, kd, vd, **kw)
             close(o, o_ref, 1.2e-2, f"attn o stage {st}")
             outs[st] = (o, lse)
     finally:
         Lb.cullavo_attn_set_stage(prev)
-    for st in (0, 1, 2, 5, 7):
-        assert torch.equal(outs[st][0], outs[4][0]), f"O stage {st} vs 4"
+    assert torch.equal(outs[7][0], outs[4][0]), "O stage 7 vs 4"
     o, lse = outs[4]
     od = nan_view(o.cpu(), 128)
     lse_d = lse  # [B, H, L] f32, read per row with its own bound
     prev_t = Lb.cullavo_attn_set_bwd_tiles(7)
-    prev_s = Lb.cullavo_attn_set_bwd_stage(0)
     try:
-        base = None
         for tiles in ((7, 4) if D == 128 else (0, 4)):
             Lb.cullavo_attn_set_bwd_tiles(tiles)
-            for st in range(16):  # bit 2: the LDS-DMA ring dQ kernel (D = 128), bit 3: blocked dS^T
-                Lb.cullavo_attn_set_bwd_stage(st)
-                dq, dk, dv = ops.attn_bwd(qd, kd, vd, od, dod, lse_d, **kw)
-                torch.cuda.synchronize()
-                tag = f"tiles {tiles} stage {st}"
-                close(dq, dq_ref, 2e-2, f"dq {tag}")
-                close(dk, dk_ref, 2e-2, f"dk {tag}")
-                close(dv, dv_ref, 2e-2, f"dv {tag}")
-                if st == 0:
-                    base = (dq, dk, dv)
-                else:
-                    for name, a, b in zip("qkv", base, (dq, dk, dv)):
-                        assert torch.equal(a, b), f"d{name} {tag} vs stage 0"
+            dq, dk, dv = ops.attn_bwd(qd, kd, vd, od, dod, lse_d, **kw)
+            torch.cuda.synchronize()
+            tag = f"tiles {tiles}"
+            close(dq, dq_ref, 2e-2, f"dq {tag}")
+            close(dk, dk_ref, 2e-2, f"dk {tag}")
+            close(dv, dv_ref, 2e-2, f"dv {tag}")
     finally:
         Lb.cullavo_attn_set_bwd_tiles(prev_t)
-        Lb.cullavo_attn_set_bwd_stage(prev_s)

@@ -1,7 +1,8 @@
-"""Forward-only A/B of the attention staging modes (cullavo_attn_set_stage) at the 7B layer and
-ViT bs-64 shapes, alternating modes over several rounds (HIP-event timing, 20 launches each).
+"""Forward-only A/B of the two attention forward kernels (cullavo_attn_set_stage: 4 plain, 7
+software-pipelined) at the 7B layer and ViT bs-64 shapes, alternating over several rounds
+(HIP-event timing, 20 launches each).
 
-  python tools/attn_fwd_ab.py [rounds] [stage ...]      (default: 4 rounds, stages 4 7)
+  python tools/attn_fwd_ab.py [rounds]      (default: 4 rounds)
 """
 import os
 import sys
@@ -12,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cullavo_amd import _lib, ops  # noqa: E402
 
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 4
-stages = [int(x) for x in sys.argv[2:]] or [4, 7]
+stages = [4, 7]
 L_ = _lib.lib()
 shapes = [("LM causal D128", 8, 1088, 32, 128, True), ("ViT D64", 64, 577, 16, 64, False)]
 data = {}

@@ -1,8 +1,12 @@
-// Lab: the dQ-from-dS^T ring kernel (attention.hip attn_bwd_dq_ring_k) at 2-4 stages, with the
+// Lab: the dQ-from-dS^T ring kernel (dq_ring.inc attn_bwd_dq_ring_k) at 2-4 stages, with the
 // fragment reads + MFMAs (LAB bit 0) and / or the K tile DMA (bit 1) left out -- timing floors that
 // say which part bounds the kernel, not results. Built by tools/lab/build_lab.sh dq_lab.hip dq;
 // loaded after libcullavo_hip.so (RTLD_GLOBAL) by tools/lab/dq_lab.py.
 #include "../../causal-unified-language-vision_amd/csrc/attention.hip"
+
+namespace {
+#include "dq_ring.inc"
+}  // namespace
 
 namespace {
 template <int NST, int LAB>

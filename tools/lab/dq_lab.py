@@ -1,5 +1,5 @@
-"""dQ ring lab (tools/lab/dq_lab.hip): the production dQ kernels (cullavo_attn_bwd_ws, mode 7, via the
-staging switch) and the lab ring variants (stages x left-out parts) on the 7B layer's shapes,
+"""dQ ring lab (tools/lab/dq_lab.hip): the ring variants (stages x left-out parts, row-major and
+blocked dS^T) of the dQ-from-dS^T kernel on the 7B layer's shapes,
 random K / dS^T, HIP-event timed, interleaved rounds.
 
   python tools/lab/dq_lab.py [--rounds 3]
