@@ -16,8 +16,8 @@ from torch import nn
 
 from . import ops
 from .config import CuLLaVOConfig
-from .functions import HeadLossFn, MergeFn, StepContext
-from .lora import LoraSettings
+from .functions import HeadLossFn, HeadLossRowsFn, MergeFn, StepContext
+from .lora import NO_LORA, LoraSettings
 from .modeling import (CLIPVisionModel, LlamaForCausalLM, LlavaMultiModalProjector, build_arenas, init_random_)
 
 
@@ -67,6 +67,9 @@ class CuLLaVOModel(nn.Module):
         self.language_model = LlamaForCausalLM(config.text_config, self.arenas["embed"], self.arenas["layers"],
                                                self.arenas["head"], la)
         self.trainable_policy = trainable
+        # the trainer's opt-in to the supervised-row tail (forward's num_supervised); off, every caller
+        # gets the full logits
+        self.supervised_rows = False
 
     @classmethod
     def from_pretrained(cls, path: str, *, device="cuda", trainable: str = "full", lora: LoraSettings | None = None,
@@ -158,7 +161,11 @@ class CuLLaVOModel(nn.Module):
     # -- forward (reference cullavo/arch_cullavo.py:546-677) ------------------------------------
     def forward(self, input_ids=None, pixel_values=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, vision_feature_layer=None, vision_feature_select_strategy=None, labels=None,
-                use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None):
+                use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None,
+                num_supervised: int | None = None):
+        """num_supervised: host-side upper bound of the number of label positions of this batch (counted
+        where the batch is built). With self.supervised_rows set (the trainer's opt-in) the loss then
+        comes from those rows only and the output carries no logits."""
         cfg = self.config
         output_hidden_states = output_hidden_states if output_hidden_states is not None else cfg.output_hidden_states
         return_dict = return_dict if return_dict is not None else cfg.use_return_dict
@@ -191,6 +198,9 @@ class CuLLaVOModel(nn.Module):
             kv_start = (attention_mask.cumsum(-1) == 0).sum(-1).to(torch.int32)
         sctx = StepContext(B, L, position_ids, kv_start)
         lm = self.language_model
+        n_rows = self._tail_rows(num_supervised, labels, B, L, output_hidden_states)
+        if n_rows:
+            return self._forward_supervised_rows(inputs_embeds, labels, attention_mask, sctx, n_rows, return_dict)
         h, hs = lm.decode(inputs_embeds.reshape(B * L, d).contiguous(), sctx, bool(output_hidden_states))  # :638
         loss = None
         if labels is not None:  # :651-665
@@ -214,6 +224,36 @@ class CuLLaVOModel(nn.Module):
             out = (logits,) + ((hs_t,) if hs_t is not None else ())
             return (loss,) + out if loss is not None else out
         return CullavoCausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=None, hidden_states=hs_t,
+                                             attentions=None)
+
+    # -- supervised-row tail: the training step's loss without the rows that carry no label ------
+    def _tail_rows(self, num_supervised, labels, B: int, L: int, output_hidden_states) -> int:
+        """padded size of the row set, or 0 for the full-logits path (the default: the switch is off,
+        no host-side count came with the batch, hidden states are wanted, or nothing would be saved)"""
+        if not self.supervised_rows or num_supervised is None or labels is None or output_hidden_states:
+            return 0
+        if tuple(labels.shape) != (B, L):
+            return 0  # the full path raises the reference's error
+        n = max(8, -(-int(num_supervised) // 8) * 8)  # K % 8 of the head's dW GEMM; zero rows pad
+        return n if n < B * L else 0
+
+    def _forward_supervised_rows(self, inputs_embeds, labels, attention_mask, sctx, n_rows: int, return_dict):
+        cfg, lm = self.config, self.language_model
+        B, L, d = inputs_embeds.shape
+        targets = ops.shift_targets(labels, attention_mask, cfg.ignore_index)
+        rows = ops.supervised_rows(targets, n_rows, cfg.ignore_index)
+        # the last layer's MLP half feeds only the head: it runs on the rows too (not under LoRA adapters)
+        last = lm.model.layers[-1]
+        compact = all(last.lora_groups[g] is NO_LORA for g in ("gu", "down"))
+        if compact:
+            sctx.tail_layer, sctx.tail_rows = last, rows
+        h, _ = lm.decode(inputs_embeds.reshape(B * L, d).contiguous(), sctx, False)
+        for ar in self.arenas.values():  # final norm / lm_head: pending optimizer updates
+            ar.wait_update()
+        loss = HeadLossRowsFn.apply(h, lm, targets, cfg.ignore_index, rows, B * L, compact, *lm.head_params())
+        if not return_dict:
+            return (loss, None)
+        return CullavoCausalLMOutputWithPast(loss=loss, logits=None, past_key_values=None, hidden_states=None,
                                              attentions=None)
 
     # -- KV-cache inference (reference :605-636 and HF generate; generation.py) ------------------

@@ -14,14 +14,29 @@ constexpr int kBwdBlocks = 256;    // backward grid (weight-grad partials: 1024 
 // PREW (few rows: the KV-cache decode step's one row per sequence): the weight row is loaded
 // together with x, before the reduction, so a launch waits out one memory round trip instead of
 // two (7.4 us per decode-step norm at one row; the many-row training launches keep the registers)
+// idx (nullable): row gather. Output row i is the norm of x[idx[i]] (idx sorted or not; the output
+// is compact), xg (nullable) also receives the gathered input row; idx[i] < 0 marks a padding row,
+// written as zeros (y, xg) with rstd 0.
 template <typename T, int NCH, bool PREW = false>
 __global__ __launch_bounds__(256) void rmsnorm_fwd_k(const T* __restrict__ x, const T* __restrict__ w,
                                                      T* __restrict__ y, float* __restrict__ rstd,
-                                                     int64_t rows, int cols, float eps) {
+                                                     int64_t rows, int cols, float eps,
+                                                     const int64_t* __restrict__ idx = nullptr,
+                                                     T* __restrict__ xg = nullptr) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const T* xr = x + row * cols;
+  const int64_t src = idx ? idx[row] : row;
+  if (src < 0) {
+    const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int col = lane * 8; col < cols; col += 512) {
+      store8(y + row * cols + col, z);
+      if (xg) store8(xg + row * cols + col, z);
+    }
+    if (lane == 0) rstd[row] = 0.f;
+    return;
+  }
+  const T* xr = x + src * cols;
   float v[NCH][8];
   float wp[PREW ? NCH : 1][8];
   float ss = 0.f;
@@ -31,6 +46,13 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_k(const T* __restrict__ x, co
     if (col < cols) {
       load8(xr + col, v[c]);
       if constexpr (PREW) load8(w + col, wp[c]);
+    }
+  }
+  if (xg) {  // values round-trip exactly (bf16 -> f32 -> bf16)
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int col = c * 512 + lane * 8;
+      if (col < cols) store8(xg + row * cols + col, v[c]);
     }
   }
 #pragma unroll
@@ -63,11 +85,29 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_k(const T* __restrict__ x, co
   }
 }
 
+// Supervised-row backward (idx != nullptr): the kernels below walk the rows of the FULL-height tensor
+// exactly as without idx (same grid, same row -> workgroup / slot / iteration), and read the compact
+// dy / x / rstd / dres row that idx maps to it; a full row without a compact row is skipped. A skipped
+// row added an exact zero to dw on the full path (its dy is zero), so dw keeps the full path's
+// summation order and comes out bitwise equal. idx [n] is ascending with -1 padding at the tail
+// (read as +inf). Returns the compact row of full row `row`, or -1.
+DEV int64_t compact_row(const int64_t* __restrict__ idx, int64_t n, int64_t row) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((uint64_t)idx[mid] < (uint64_t)row) lo = mid + 1;
+    else hi = mid;
+  }
+  return (lo < n && idx[lo] == row) ? lo : -1;
+}
+
 template <typename T, int NCH, bool WANT_DW, bool HAS_DRES>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_k(const T* __restrict__ dy, const T* __restrict__ x,
                                                      const T* __restrict__ w, const float* __restrict__ rstd,
                                                      T* __restrict__ dx, const T* __restrict__ dres,
-                                                     float* __restrict__ part, int64_t rows, int cols) {
+                                                     float* __restrict__ part, int64_t rows, int cols,
+                                                     const int64_t* __restrict__ idx = nullptr, int64_t n = 0,
+                                                     bool compact_out = false) {
   const int lane = threadIdx.x & 63;
   const int wslot = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
   const int nslots = gridDim.x * kRowsPerBlock;
@@ -82,7 +122,10 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_k(const T* __restrict__ dy, c
     const int col = c * 512 + lane * 8;
     if (col < cols) load8(w + col, wv[c]);
   }
-  for (int64_t row = wslot; row < rows; row += nslots) {
+  for (int64_t frow = wslot; frow < rows; frow += nslots) {
+    const int64_t row = idx ? compact_row(idx, n, frow) : frow;  // the row read; < 0: no compact row
+    if (row < 0) continue;
+    const int64_t orow = compact_out ? row : frow;
     const float r = rstd[row];
     float xv[NCH][8], g[NCH][8];
     float dot = 0.f;
@@ -116,7 +159,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_k(const T* __restrict__ dy, c
 #pragma unroll
           for (int j = 0; j < 8; ++j) o[j] += rr[j];
         }
-        store8(dx + row * cols + col, o);
+        store8(dx + orow * cols + col, o);
       }
     }
   }
@@ -156,7 +199,9 @@ __global__ __launch_bounds__(512, WANT_DW ? 2 : 4) void rmsnorm_bwd8_k(const T* 
                                                          const T* __restrict__ w, const float* __restrict__ rstd,
                                                          T* __restrict__ dx, const T* __restrict__ dres,
                                                          float* __restrict__ part, int64_t rows, int cols,
-                                                         int64_t rows_per_block) {
+                                                         int64_t rows_per_block,
+                                                         const int64_t* __restrict__ idx = nullptr, int64_t n = 0,
+                                                         bool compact_out = false) {
   // two waves per row (wave = 2*slot + half; half h owns the 512-column chunks c = h, h+2, ...),
   // four rows in flight per workgroup, the row's dot product combined through LDS
   constexpr int NH = (NCH + 1) / 2;  // chunks per half
@@ -173,8 +218,10 @@ __global__ __launch_bounds__(512, WANT_DW ? 2 : 4) void rmsnorm_bwd8_k(const T* 
     for (int j = 0; j < 8; ++j) acc[c][j] = 0.f;
   const int iters = (int)cdiv(r1 - r0, (int64_t)4);
   for (int it = 0; it < iters; ++it) {
-    const int64_t row = r0 + 4 * it + slot;
-    const bool live = row < r1;
+    const int64_t frow = r0 + 4 * it + slot;
+    const int64_t row = frow < r1 ? (idx ? compact_row(idx, n, frow) : frow) : -1;  // the row read; < 0: skipped
+    const bool live = row >= 0;
+    const int64_t orow = compact_out ? row : frow;
     const float r = live ? rstd[row] : 0.f;
     Raw8<T> xr[NH], dr[NH], rr[NH];
 #pragma unroll
@@ -217,7 +264,7 @@ __global__ __launch_bounds__(512, WANT_DW ? 2 : 4) void rmsnorm_bwd8_k(const T* 
           o[j] = r * (dr[c][j] * wr[j] - xr[c][j] * r * dot);
           if (HAS_DRES) o[j] += rr[c][j];
         }
-        store8(dx + row * cols + col, o);
+        store8(dx + orow * cols + col, o);
       }
     }
   }
@@ -254,8 +301,12 @@ template <typename T, int NH, bool HAS_DRES>
 struct BwdRows {
   Raw8<T> xr[NH], dr[NH], rr[NH];
   float r;
-  DEV void load(const T* x, const T* dy, const T* dres, const float* rstd, int64_t row, bool live, int part,
-                int lane, int nch, int cols) {
+  int64_t orow;  // the row dx is written to, -1 when not live
+  DEV void load(const T* x, const T* dy, const T* dres, const float* rstd, const int64_t* idx, int64_t n,
+                bool compact_out, int64_t frow, bool live, int part, int lane, int nch, int cols) {
+    const int64_t row = live ? (idx ? compact_row(idx, n, frow) : frow) : -1;  // the row read
+    live = row >= 0;
+    orow = live ? (compact_out ? row : frow) : -1;
     r = live ? rstd[row] : 0.f;
 #pragma unroll
     for (int c = 0; c < NH; ++c) {
@@ -274,7 +325,9 @@ __global__ __launch_bounds__(512, 1) void rmsnorm_bwd8p_k(const T* __restrict__ 
                                                           const T* __restrict__ w, const float* __restrict__ rstd,
                                                           T* __restrict__ dx, const T* __restrict__ dres,
                                                           float* __restrict__ part, int64_t rows, int cols,
-                                                          int64_t rows_per_block) {
+                                                          int64_t rows_per_block,
+                                                          const int64_t* __restrict__ idx = nullptr, int64_t n = 0,
+                                                          bool compact_out = false) {
   constexpr int NH = (NCH + kWpr - 1) / kWpr;
   extern __shared__ float sdw[];
   __shared__ float pdot[2][kSlots][kWpr];
@@ -290,8 +343,8 @@ __global__ __launch_bounds__(512, 1) void rmsnorm_bwd8p_k(const T* __restrict__ 
   const int iters = (int)cdiv(max(r1 - r0, (int64_t)0), (int64_t)kSlots);
 
   auto body = [&](const BwdRows<T, NH, HAS_DRES>& cur, int it) {
-    const int64_t row = r0 + kSlots * it + slot;
-    const bool live = row < r1;
+    const int64_t orow = cur.orow;  // < 0: past the chunk, or a full row without a compact row
+    const bool live = orow >= 0;
     const float r = cur.r;
     float dot = 0.f;
 #pragma unroll
@@ -327,13 +380,13 @@ __global__ __launch_bounds__(512, 1) void rmsnorm_bwd8p_k(const T* __restrict__ 
           o[j] = r * (cur.dr[c][j] * wr[j] - cur.xr[c][j] * r * dot);
           if (HAS_DRES) o[j] += cur.rr[c][j];
         }
-        store8(dx + row * cols + col, o);
+        store8(dx + orow * cols + col, o);
       }
     }
   };
   auto load = [&](BwdRows<T, NH, HAS_DRES>& dst, int it) {
     const int64_t row = r0 + kSlots * it + slot;
-    dst.load(x, dy, dres, rstd, row, it < iters && row < r1, wp, lane, NCH, cols);
+    dst.load(x, dy, dres, rstd, idx, n, compact_out, row, it < iters && row < r1, wp, lane, NCH, cols);
   };
 
   BwdRows<T, NH, HAS_DRES> ra, rb;
@@ -359,6 +412,26 @@ __global__ __launch_bounds__(512, 1) void rmsnorm_bwd8p_k(const T* __restrict__ 
       __syncthreads();
     }
     for (int col = threadIdx.x; col < cols; col += 512) part[(int64_t)blockIdx.x * cols + col] = sdw[col];
+  }
+}
+
+// The rows of a full-height tensor around a compact one, one wave per row. A full row with a compact
+// row (idx) receives src's compact row, or is left to the scattered RMSNorm backward when src is
+// null; every other row becomes zero, or dres_full's row when given.
+template <typename T>
+__global__ __launch_bounds__(256) void rows_fill_k(T* __restrict__ dx, const T* __restrict__ dres_full,
+                                                   const T* __restrict__ src, const int64_t* __restrict__ idx,
+                                                   int64_t n, int64_t full_rows, int64_t cols) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+  if (row >= full_rows) return;
+  const int64_t ci = compact_row(idx, n, row);
+  if (ci >= 0 && !src) return;  // the norm backward writes this row
+  for (int64_t col = lane * 8; col < cols; col += 512) {
+    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (ci >= 0) load8(src + ci * cols + col, o);
+    else if (dres_full) load8(dres_full + row * cols + col, o);
+    store8(dx + row * cols + col, o);
   }
 }
 
@@ -545,8 +618,8 @@ extern "C" size_t cullavo_norm_bwd_workspace(int64_t rows, int64_t cols) {
   return (size_t)2 * kBwdBlocks * kRowsPerBlock * cols * sizeof(float);
 }
 
-extern "C" int cullavo_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int64_t rows,
-                                   int64_t cols, float eps, int dtype, void* stream) {
+static int rmsnorm_fwd_impl(const void* x, const int64_t* idx, const void* w, void* y, float* rstd, void* xg,
+                            int64_t rows, int64_t cols, float eps, int dtype, void* stream) {
   CV_REQUIRE(cols % 8 == 0 && cols > 0 && cols <= 8192, CULLAVO_EINVAL, "cols must be a multiple of 8 in [8, 8192]");
   CV_REQUIRE(rows >= 0, CULLAVO_EINVAL, "rows < 0");
   if (rows == 0) return CULLAVO_OK;
@@ -554,15 +627,27 @@ extern "C" int cullavo_rmsnorm_fwd(const void* x, const void* w, void* y, float*
   hipStream_t s = CV_STREAM(stream);
   const int nch = nch_for(cols);
   if (dtype == CULLAVO_DT_BF16 && rows <= 64 && nch <= 8) {
-    NCH_DISPATCH(nch, rmsnorm_fwd_k<u16, NC, true><<<nb, 256, 0, s>>>((const u16*)x, (const u16*)w, (u16*)y, rstd, rows, (int)cols, eps));
+    NCH_DISPATCH(nch, rmsnorm_fwd_k<u16, NC, true><<<nb, 256, 0, s>>>((const u16*)x, (const u16*)w, (u16*)y, rstd, rows, (int)cols, eps, idx, (u16*)xg));
   } else if (dtype == CULLAVO_DT_BF16) {
-    NCH_DISPATCH(nch, rmsnorm_fwd_k<u16, NC><<<nb, 256, 0, s>>>((const u16*)x, (const u16*)w, (u16*)y, rstd, rows, (int)cols, eps));
+    NCH_DISPATCH(nch, rmsnorm_fwd_k<u16, NC><<<nb, 256, 0, s>>>((const u16*)x, (const u16*)w, (u16*)y, rstd, rows, (int)cols, eps, idx, (u16*)xg));
   } else if (dtype == CULLAVO_DT_F32) {
-    NCH_DISPATCH(nch, rmsnorm_fwd_k<float, NC><<<nb, 256, 0, s>>>((const float*)x, (const float*)w, (float*)y, rstd, rows, (int)cols, eps));
+    NCH_DISPATCH(nch, rmsnorm_fwd_k<float, NC><<<nb, 256, 0, s>>>((const float*)x, (const float*)w, (float*)y, rstd, rows, (int)cols, eps, idx, (float*)xg));
   } else {
     CV_REQUIRE(false, CULLAVO_EUNSUPPORTED, "dtype");
   }
   return cullavo_check_launch("rmsnorm_fwd");
+}
+
+extern "C" int cullavo_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int64_t rows,
+                                   int64_t cols, float eps, int dtype, void* stream) {
+  return rmsnorm_fwd_impl(x, nullptr, w, y, rstd, nullptr, rows, cols, eps, dtype, stream);
+}
+
+extern "C" int cullavo_rmsnorm_fwd_rows(const void* x, const int64_t* rows_idx, const void* w, void* y,
+                                        float* rstd, void* x_rows, int64_t n, int64_t cols, float eps,
+                                        int dtype, void* stream) {
+  CV_REQUIRE(rows_idx != nullptr || n == 0, CULLAVO_EINVAL, "rows_idx is null");
+  return rmsnorm_fwd_impl(x, rows_idx, w, y, rstd, x_rows, n, cols, eps, dtype, stream);
 }
 
 static int g_rms_bwd_mode = 1;  // 1 = pipelined 8-wave kernel (default), 0 = rmsnorm_bwd8_k
@@ -573,13 +658,32 @@ extern "C" int cullavo_rmsnorm_set_bwd(int mode) {
   return prev;
 }
 
-extern "C" int cullavo_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd,
-                                   void* dx, const void* dres, void* dw, int w_dtype, float beta, float* ws,
-                                   int64_t rows, int64_t cols, int dtype, void* stream) {
+// by_rows: the supervised-row form (cullavo_rmsnorm_bwd_rows): dy, x, rstd, dres have n compact rows, the
+// kernels walk full_rows rows. dx then has full_rows rows (compact row i goes to row idx[i], every
+// other row is filled with zero or dres_full's row), or stays compact [n, cols] under compact_out.
+static int rmsnorm_bwd_impl(const void* dy, const void* x, const void* w, const float* rstd, void* dx,
+                            const void* dres, bool by_rows, const int64_t* idx, int64_t n, bool compact_out, const void* dres_full,
+                            void* dw, int w_dtype, float beta, float* ws, int64_t rows, int64_t cols, int dtype,
+                            void* stream) {
+  const bool scatter = by_rows && !compact_out;
+  const int64_t full_rows = rows;
   CV_REQUIRE(cols % 8 == 0 && cols > 0 && cols <= 8192, CULLAVO_EINVAL, "cols must be a multiple of 8 in [8, 8192]");
   CV_REQUIRE(dw == nullptr || ws != nullptr, CULLAVO_EINVAL, "dw requires a workspace");
-  if (rows == 0) return CULLAVO_OK;
+  CV_REQUIRE(dtype == CULLAVO_DT_BF16 || dtype == CULLAVO_DT_F32, CULLAVO_EUNSUPPORTED, "dtype");
   hipStream_t s = CV_STREAM(stream);
+  if (scatter && full_rows > 0) {
+    const int nbf = (int)cdiv(full_rows, kRowsPerBlock);
+    if (dtype == CULLAVO_DT_BF16) rows_fill_k<u16><<<nbf, 256, 0, s>>>((u16*)dx, (const u16*)dres_full, nullptr, idx, n, full_rows, cols);
+    else rows_fill_k<float><<<nbf, 256, 0, s>>>((float*)dx, (const float*)dres_full, nullptr, idx, n, full_rows, cols);
+  }
+  if (rows == 0 || (by_rows && n == 0)) {
+    // nothing to reduce over; a supervised-row call still owes dw its beta-scaled (or zero) value
+    if (by_rows && dw != nullptr) {
+      if (w_dtype == CULLAVO_DT_BF16) launch_reduce<u16>(ws, 0, (int)cols, dw, beta, s);
+      else launch_reduce<float>(ws, 0, (int)cols, dw, beta, s);
+    }
+    return by_rows ? cullavo_check_launch("rmsnorm_bwd") : CULLAVO_OK;
+  }
   const int nch = nch_for(cols);
   const bool want = dw != nullptr, hr = dres != nullptr;
   // more than 4096 columns (Llama-2-13B's 5120): the pipelined kernel with four waves per row
@@ -593,17 +697,15 @@ extern "C" int cullavo_rmsnorm_bwd(const void* dy, const void* x, const void* w,
   const int64_t rpb = cdiv(rows, nb);
   const size_t lds = want ? (size_t)cols * sizeof(float) : 0;
 #define RMB(T, WD, HR)                                                                                        \
-  if (wide) rmsnorm_bwd_k<T, 16, WD, HR><<<nb, 256, 0, s>>>((const T*)dy, (const T*)x, (const T*)w, rstd, (T*)dx, (const T*)dres, ws, rows, (int)cols); \
-  else if (pipe) NCH_DISPATCH(nch, rmsnorm_bwd8p_k<T, NC, WD, HR><<<nb, 512, lds, s>>>((const T*)dy, (const T*)x, (const T*)w, rstd, (T*)dx, (const T*)dres, ws, rows, (int)cols, rpb)) \
-  else NCH_DISPATCH(nch, rmsnorm_bwd8_k<T, (NC > 8 ? 8 : NC), WD, HR><<<nb, 512, lds, s>>>((const T*)dy, (const T*)x, (const T*)w, rstd, (T*)dx, (const T*)dres, ws, rows, (int)cols, rpb))
+  if (wide) rmsnorm_bwd_k<T, 16, WD, HR><<<nb, 256, 0, s>>>((const T*)dy, (const T*)x, (const T*)w, rstd, (T*)dx, (const T*)dres, ws, rows, (int)cols, idx, n, compact_out); \
+  else if (pipe) NCH_DISPATCH(nch, rmsnorm_bwd8p_k<T, NC, WD, HR><<<nb, 512, lds, s>>>((const T*)dy, (const T*)x, (const T*)w, rstd, (T*)dx, (const T*)dres, ws, rows, (int)cols, rpb, idx, n, compact_out)) \
+  else NCH_DISPATCH(nch, rmsnorm_bwd8_k<T, (NC > 8 ? 8 : NC), WD, HR><<<nb, 512, lds, s>>>((const T*)dy, (const T*)x, (const T*)w, rstd, (T*)dx, (const T*)dres, ws, rows, (int)cols, rpb, idx, n, compact_out))
   if (dtype == CULLAVO_DT_BF16) {
     if (want && hr) { RMB(u16, true, true); } else if (want) { RMB(u16, true, false); }
     else if (hr) { RMB(u16, false, true); } else { RMB(u16, false, false); }
-  } else if (dtype == CULLAVO_DT_F32) {
+  } else {
     if (want && hr) { RMB(float, true, true); } else if (want) { RMB(float, true, false); }
     else if (hr) { RMB(float, false, true); } else { RMB(float, false, false); }
-  } else {
-    CV_REQUIRE(false, CULLAVO_EUNSUPPORTED, "dtype");
   }
 #undef RMB
   if (want) {
@@ -612,6 +714,40 @@ extern "C" int cullavo_rmsnorm_bwd(const void* dy, const void* x, const void* w,
     else launch_reduce<float>(ws, nslots, (int)cols, dw, beta, s);
   }
   return cullavo_check_launch("rmsnorm_bwd");
+}
+
+extern "C" int cullavo_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd,
+                                   void* dx, const void* dres, void* dw, int w_dtype, float beta, float* ws,
+                                   int64_t rows, int64_t cols, int dtype, void* stream) {
+  return rmsnorm_bwd_impl(dy, x, w, rstd, dx, dres, false, nullptr, 0, false, nullptr, dw, w_dtype, beta, ws, rows, cols, dtype,
+                          stream);
+}
+
+extern "C" int cullavo_rmsnorm_bwd_rows(const void* dy, const void* x, const void* w, const float* rstd,
+                                        const void* dres, const int64_t* rows_idx, void* dx_full,
+                                        const void* dres_full, int64_t full_rows, int compact_out, void* dw,
+                                        int w_dtype, float beta, float* ws, int64_t n, int64_t cols, int dtype,
+                                        void* stream) {
+  CV_REQUIRE(rows_idx != nullptr || n == 0, CULLAVO_EINVAL, "rows_idx is null");
+  CV_REQUIRE(n >= 0 && full_rows >= 0, CULLAVO_EINVAL, "n or full_rows < 0");
+  CV_REQUIRE(!compact_out || dres_full == nullptr, CULLAVO_EINVAL, "dres_full with a compact dx");
+  return rmsnorm_bwd_impl(dy, x, w, rstd, dx_full, dres, true, rows_idx, n, compact_out != 0, dres_full, dw, w_dtype, beta, ws,
+                          full_rows, cols, dtype, stream);
+}
+
+extern "C" int cullavo_rows_scatter(const void* src, const int64_t* rows_idx, void* dst, int64_t n,
+                                    int64_t full_rows, int64_t cols, int dtype, void* stream) {
+  CV_REQUIRE(cols % 8 == 0 && cols > 0, CULLAVO_EINVAL, "cols must be a positive multiple of 8");
+  CV_REQUIRE((rows_idx != nullptr || n == 0) && n >= 0 && full_rows >= 0, CULLAVO_EINVAL, "rows_idx is null, or n or full_rows < 0");
+  CV_REQUIRE(src != nullptr || n == 0, CULLAVO_EINVAL, "src is null");
+  CV_REQUIRE(dtype == CULLAVO_DT_BF16 || dtype == CULLAVO_DT_F32, CULLAVO_EUNSUPPORTED, "dtype");
+  if (full_rows == 0) return CULLAVO_OK;
+  hipStream_t s = CV_STREAM(stream);
+  const int nbf = (int)cdiv(full_rows, kRowsPerBlock);
+  // n = 0 with a null src: compact_row finds nothing, every row is zeroed
+  if (dtype == CULLAVO_DT_BF16) rows_fill_k<u16><<<nbf, 256, 0, s>>>((u16*)dst, nullptr, (const u16*)src, rows_idx, n, full_rows, cols);
+  else rows_fill_k<float><<<nbf, 256, 0, s>>>((float*)dst, nullptr, (const float*)src, rows_idx, n, full_rows, cols);
+  return cullavo_check_launch("rows_scatter");
 }
 
 extern "C" int cullavo_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean,

@@ -4,7 +4,9 @@ The reference builds each batch on the CPU from COCO/ShareGPT4V images with dete
 the llava tokenizer and CLIPImageProcessor (reference cullavo/arch_cullavo.py:96-339, 397-543;
 out of scope: real tokenizer/images are unavailable offline). What reaches the hot path is
 fixed tensors: input_ids [B, S] with one <image> id per row, attention_mask, pixel_values
-[B, 3, 336, 336] and labels at the merged length [B, S + P - 1] (-100 on the prompt).
+[B, 3, 336, 336], labels at the merged length [B, S + P - 1] (-100 on the prompt) and the host-side
+count of label positions, num_supervised (an upper bound is enough: the supervised-row tail sizes its
+compact buffers from it).
 Batches are generated directly in HBM so the timed step starts with resident inputs.
 """
 from __future__ import annotations
@@ -34,7 +36,11 @@ def synthetic_batch(cfg: CuLLaVOConfig, batch: int, text_len: int = 513, image_c
     labels = torch.full((batch, L), cfg.ignore_index, dtype=torch.long, device=device)
     labels[:, label_from:] = torch.randint(2, cfg.image_token_index, (batch, L - label_from), generator=g,
                                            device=device)
-    return {"input_ids": ids, "attention_mask": mask, "pixel_values": pix, "labels": labels}
+    # host-side count of the label positions the shifted loss reads (positions >= 1), taken here with
+    # the labels so the step never asks the device for it (CuLLaVOModel.forward num_supervised)
+    n_sup = batch * (L - max(label_from, 1))
+    return {"input_ids": ids, "attention_mask": mask, "pixel_values": pix, "labels": labels,
+            "num_supervised": n_sup}
 
 
 class SyntheticLoader:

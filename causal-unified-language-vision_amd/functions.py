@@ -9,6 +9,7 @@ straight into the arena (arena.grad_slot) and returns only activation gradients.
   EmbeddingFn       embed_tokens        reference cullavo/arch_cullavo.py:582
   MergeFn           _merge_input_ids_with_image_features rows   arch_cullavo.py:600-602
   HeadLossFn        final RMSNorm + lm_head + shifted masked CE   arch_cullavo.py:651-665
+  HeadLossRowsFn    the same loss from the rows with a label only (no logits output)
 
 Parameters are passed to .apply only so autograd sees a dependency; their returned gradient
 is None (the value is already in the arena).
@@ -183,9 +184,13 @@ class LinearFn(torch.autograd.Function):
 class StepContext:
     """Per-forward shape/index state shared by the decoder layers (built once per step).
     lora_seed: this forward's LoRA-dropout seed (drawn from torch's CPU generator, so
-    torch.manual_seed makes runs repeatable; backward reuses it to regenerate the masks)."""
+    torch.manual_seed makes runs repeatable; backward reuses it to regenerate the masks).
+    tail_layer / tail_rows: the supervised-row tail (ops.supervised_rows): the decoder layer that runs
+    its MLP half on the rows tail_rows only and returns the compact [n, d] hidden state (the last layer,
+    set by the caller together with HeadLossRowsFn; None: every layer runs at full height)."""
 
     def __init__(self, B: int, L: int, position_ids, kv_start=None, lora_seed: int | None = None):
+        self.tail_layer, self.tail_rows = None, None
         self.B, self.L = B, L
         self.position_ids = position_ids.reshape(-1).contiguous()
         self.kv_start = kv_start
@@ -211,7 +216,17 @@ class LlamaLayerFn(torch.autograd.Function):
                               kv_start=sctx.kv_start)
         t, u_o = lg["o"].forward(o, tr, seed)
         h2 = ops.linear(o, layer.self_attn.o_proj.weight, residual=h, addend=t)
-        x2, rstd2 = ops.rmsnorm_fwd(h2, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
+        # supervised-row tail: the MLP half of this layer feeds only the head, which reads the rows
+        # with a label; gather them with the norm (compact x2, rstd2, h2) and return a compact h3.
+        # The attention half above is unchanged: every row is a key and a value.
+        rows = sctx.tail_rows if sctx.tail_layer is layer else None
+        if rows is not None:
+            if lg["gu"] is not NO_LORA or lg["down"] is not NO_LORA:
+                raise ValueError("the supervised-row tail does not cover LoRA adapters on the MLP")
+            x2, rstd2, h2 = ops.rmsnorm_fwd_rows(h2, rows, layer.post_attention_layernorm.weight, cfg.rms_norm_eps,
+                                                 want_rows=True)
+        else:
+            x2, rstd2 = ops.rmsnorm_fwd(h2, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
         t, u_gu = lg["gu"].forward(x2, tr, seed)
         gu = ops.linear(x2, layer.w_gu(), addend=t)  # [T, 2F]: gate | up
         a = ops.swiglu_fwd(gu)
@@ -220,7 +235,7 @@ class LlamaLayerFn(torch.autograd.Function):
         del t
         _span_end(span, "fwd")
         if grad:
-            ctx.layer, ctx.sctx, ctx.train = layer, sctx, tr
+            ctx.layer, ctx.sctx, ctx.train, ctx.rows = layer, sctx, tr, rows
             ctx.saved = (h, x1, rstd1, qkv, o, lse, h2, x2, rstd2, gu, a, u_qkv, u_o, u_gu, u_d)
         return h3
 
@@ -240,8 +255,11 @@ class LlamaLayerFn(torch.autograd.Function):
         # share first (bitwise the same arithmetic either way, tests/test_ops_gpu.py).
         fused_swg = lg["down"] is NO_LORA and FUSED_SWIGLU_BWD and gu.dtype == torch.bfloat16
         overlap = fused_swg and SWG_OVERLAP and dh3.is_cuda
+        # supervised-row tail: the dW GEMMs read their operands at full height, zero in the rows without
+        # a label, so K keeps the full path's summation order and the gradients stay bitwise the same
+        full = (lambda t: ops.rows_scatter(t, ctx.rows, T)) if ctx.rows is not None else (lambda t: t)
         if overlap:
-            _write_dw(dh3, a, layer.mlp.down_proj.weight, side=True)
+            _write_dw(full(dh3), full(a), layer.mlp.down_proj.weight, side=True)
         if fused_swg:
             dgu = layer.linear_dx(dh3, "down", swiglu_gu=gu)
         else:
@@ -250,16 +268,19 @@ class LlamaLayerFn(torch.autograd.Function):
             dgu = ops.swiglu_bwd(da, gu)
             del da
         if not overlap:
-            _write_dw(dh3, a, layer.mlp.down_proj.weight)
+            _write_dw(full(dh3), full(a), layer.mlp.down_proj.weight)
         dx2 = layer.linear_dx(dgu, "gu")
         lg["gu"].backward(dgu, x2, u_gu, dx2, tr, seed)
         if trainable(layer.mlp.gate_proj.weight):
             g, beta = layer.gu_grad_slot()
-            _dw(dgu, x2, g, beta, layer.mlp.gate_proj.weight, layer.mlp.up_proj.weight)
+            _dw(full(dgu), full(x2), g, beta, layer.mlp.gate_proj.weight, layer.mlp.up_proj.weight)
         del dgu
         wpost = layer.post_attention_layernorm.weight
         dw_post, beta_post = grad_slot(wpost) if trainable(wpost) else (None, 0.0)
-        dh2 = ops.rmsnorm_bwd(dx2, h2, wpost, rstd2, dres=dh3, dw=dw_post, beta=beta_post)
+        if ctx.rows is not None:  # compact MLP half: dh2 at full height, zero in the rows without a label
+            dh2 = ops.rmsnorm_bwd_rows(dx2, h2, wpost, rstd2, ctx.rows, T, dres=dh3, dw=dw_post, beta=beta_post)
+        else:
+            dh2 = ops.rmsnorm_bwd(dx2, h2, wpost, rstd2, dres=dh3, dw=dw_post, beta=beta_post)
         commit(wpost)
         del dx2
         # attention
@@ -484,3 +505,55 @@ class HeadLossFn(torch.autograd.Function):
         dh = ops.rmsnorm_bwd(dx, h, norm_w, rstd, dw=dw, beta=beta) if ctx.needs_input_grad[0] else None
         commit(norm_w)
         return (dh, None, None, None) + (None,) * len(lm.head_params())
+
+
+class HeadLossRowsFn(torch.autograd.Function):
+    """HeadLossFn over the supervised rows only, for a step that does not read the logits: final
+    RMSNorm (gathering the rows when h is at full height) -> lm_head at M = n -> CE on the compact
+    targets -> mean. rows: ops.supervised_rows (ascending, -1 padding, n % 8 == 0); a row without a
+    label contributed an exact zero to every gradient on the full path, and the weight gradients here
+    are summed in the full path's order (zero rows scattered back in), so they are bitwise the same. compact_in: h is already [n, d] (the last layer ran its tail on rows)."""
+
+    @staticmethod
+    def forward(ctx, h, lm, targets, ignore_index: int, rows, full_rows: int, compact_in: bool, *params):
+        norm_w, W = lm.model.norm.weight, lm.lm_head.weight
+        eps = lm.cfg.rms_norm_eps
+        if rows.numel() % 8:
+            raise ValueError("HeadLossRowsFn: pad the row set to a multiple of 8")
+        tc = ops.gather_targets(targets, rows, ignore_index)
+        if compact_in:
+            x, rstd = ops.rmsnorm_fwd(h, norm_w, eps)
+            hc = h
+        else:
+            x, rstd, hc = ops.rmsnorm_fwd_rows(h, rows, norm_w, eps, want_rows=True)
+        logits = ops.linear(x, W)
+        row_loss, lse = ops.ce_fwd(logits, tc, ignore_index)
+        out = ops.ce_reduce(row_loss, tc, ignore_index)
+        ctx.lm, ctx.ignore = lm, ignore_index
+        ctx.rows, ctx.full_rows, ctx.compact_in = rows, full_rows, compact_in
+        ctx.saved = (hc, x, rstd, logits, tc, lse, out)
+        ctx.stats = out  # [loss, count, 1/count] on device (no host sync)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lm = ctx.lm
+        hc, x, rstd, logits, tc, lse, out = ctx.saved
+        ctx.saved = None
+        norm_w, W = lm.model.norm.weight, lm.lm_head.weight
+        gl = dloss.reshape(1).float().contiguous()
+        dl = ops.ce_bwd(logits, tc, lse, out, gl, ctx.ignore)
+        dx = ops.linear_dx(dl, W)
+        if trainable(W):  # at full height: the full path's K order (bitwise the same head gradient)
+            _write_dw(ops.rows_scatter(dl, ctx.rows, ctx.full_rows), ops.rows_scatter(x, ctx.rows, ctx.full_rows), W)
+        del dl
+        dw, beta = grad_slot(norm_w) if trainable(norm_w) else (None, 0.0)
+        dh = None
+        if ctx.needs_input_grad[0]:
+            if ctx.compact_in:
+                dh = ops.rmsnorm_bwd_rows(dx, hc, norm_w, rstd, ctx.rows, ctx.full_rows, dw=dw, beta=beta,
+                                          compact_out=True)
+            else:
+                dh = ops.rmsnorm_bwd_rows(dx, hc, norm_w, rstd, ctx.rows, ctx.full_rows, dw=dw, beta=beta)
+        commit(norm_w)
+        return (dh, None, None, None, None, None, None) + (None,) * len(lm.head_params())

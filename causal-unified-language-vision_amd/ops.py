@@ -17,7 +17,8 @@ from ._lib import ACT_GELU, ACT_NONE, ACT_QUICK_GELU, ACT_SWIGLU_BWD, DT_BF16, D
 
 __all__ = [
     "ACT_NONE", "ACT_GELU", "ACT_QUICK_GELU", "ACT_SWIGLU_BWD", "gemm", "gemm_ex", "linear", "linear_dx", "linear_dx_t", "transpose2d", "linear_dw",
-    "rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fwd", "swiglu_bwd",
+    "rmsnorm_fwd", "rmsnorm_bwd", "supervised_rows", "gather_targets", "rmsnorm_fwd_rows", "rmsnorm_bwd_rows", "rows_scatter",
+    "layernorm_fwd", "layernorm_bwd", "swiglu_fwd", "swiglu_bwd",
     "act_bwd", "colsum", "rope", "attn_fwd", "attn_bwd", "embedding_fwd", "embedding_bwd",
     "im2col_patches", "vision_embed_ln", "merge_plan", "row_gather2", "shift_targets", "ce_fwd",
     "ce_reduce", "ce_bwd", "adamw", "sumsq", "clip_coef", "scale_inplace", "kv_append", "attn_decode",
@@ -312,6 +313,73 @@ def rmsnorm_bwd(dy, x, w, rstd, *, dres=None, dw=None, beta: float = 0.0):
     call("rmsnorm_bwd", _ptr(dy), _ptr(x), _ptr(w), _ptr(rstd), _ptr(dx), _ptr(dres), _ptr(dw),
          _dt(dw) if dw is not None else DT_BF16, float(beta), _ptr(ws), rows, cols, _dt(x), _stream())
     return dx
+
+
+def supervised_rows(targets, n: int, ignore_index: int = -100):
+    """Row set of the supervised-row tail: [n] int64, the ascending indices of targets != ignore_index,
+    then -1 padding. n is a host-side upper bound of their count (taken where the batch is built), so
+    nothing here synchronises; indices past n would be dropped, which a true upper bound rules out."""
+    _dev(targets)
+    t = targets.reshape(-1)
+    valid = t != ignore_index
+    pos = torch.cumsum(valid, 0) - 1
+    rows = torch.full((n + 1,), -1, dtype=torch.int64, device=t.device)  # slot n: the unsupervised rows' sink
+    rows.scatter_(0, torch.where(valid & (pos < n), pos, n), torch.arange(t.numel(), device=t.device))
+    return rows[:n]
+
+
+def gather_targets(targets, rows, ignore_index: int = -100):
+    """targets of the compact rows (padding rows: ignore_index)"""
+    t = targets.reshape(-1)[rows.clamp_min(0)]
+    return torch.where(rows >= 0, t, ignore_index).contiguous()
+
+
+def rmsnorm_fwd_rows(x, rows, w, eps: float, *, want_rows: bool = False):
+    """(y, rstd[, x_rows]) of the rows x[rows] (cullavo_rmsnorm_fwd_rows): gather and norm in one pass;
+    want_rows also returns the gathered input rows. Padding entries (-1) give zero rows."""
+    _dev(x, rows, w)
+    if rows.dtype != torch.int64 or not rows.is_contiguous():
+        raise ValueError("rmsnorm_fwd_rows: rows must be a contiguous int64 vector")
+    n, cols = rows.numel(), x.shape[1]
+    y = torch.empty((n, cols), dtype=x.dtype, device=x.device)
+    rstd = torch.empty(n, dtype=torch.float32, device=x.device)
+    xg = torch.empty_like(y) if want_rows else None
+    call("rmsnorm_fwd_rows", _ptr(x), _ptr(rows), _ptr(w), _ptr(y), _ptr(rstd), _ptr(xg), n, cols, float(eps),
+         _dt(x), _stream())
+    return (y, rstd, xg) if want_rows else (y, rstd)
+
+
+def rmsnorm_bwd_rows(dy, x, w, rstd, rows, full_rows: int, *, dres=None, dres_full=None, dw=None,
+                     beta: float = 0.0, compact_out: bool = False):
+    """cullavo_rmsnorm_bwd_rows: rmsnorm_bwd over the compact dy / x / rstd / dres, dx scattered to a
+    [full_rows, cols] tensor whose other rows are zero (or dres_full's); compact_out: dx stays [n, cols]
+    (padding rows zero). dw is summed in the full-height kernel's order (bitwise the full path's)."""
+    _dev(dy, x, w, rstd, rows, dres, dres_full, dw)
+    n, cols = x.shape
+    if rows.numel() != n or rows.dtype != torch.int64 or not rows.is_contiguous():
+        raise ValueError("rmsnorm_bwd_rows: rows must be a contiguous int64 vector, one entry per compact row")
+    if dres_full is not None and (compact_out or tuple(dres_full.shape) != (full_rows, cols)):
+        raise ValueError(f"rmsnorm_bwd_rows: dres_full {tuple(dres_full.shape)} != {(full_rows, cols)}, or compact_out")
+    if compact_out:
+        dx = torch.zeros((n, cols), dtype=x.dtype, device=x.device)
+    else:
+        dx = torch.empty((full_rows, cols), dtype=x.dtype, device=x.device)
+    ws = _norm_ws(full_rows, cols, x.device) if dw is not None else None
+    call("rmsnorm_bwd_rows", _ptr(dy), _ptr(x), _ptr(w), _ptr(rstd), _ptr(dres), _ptr(rows), _ptr(dx),
+         _ptr(dres_full), full_rows, int(compact_out), _ptr(dw), _dt(dw) if dw is not None else DT_BF16, float(beta),
+         _ptr(ws), n, cols, _dt(x), _stream())
+    return dx
+
+
+def rows_scatter(src, rows, full_rows: int):
+    """cullavo_rows_scatter: [full_rows, cols] with src's compact row i in row rows[i], zeros elsewhere"""
+    _dev(src, rows)
+    n, cols = src.shape
+    if rows.numel() != n or rows.dtype != torch.int64 or not rows.is_contiguous() or not src.is_contiguous():
+        raise ValueError("rows_scatter: contiguous src and a contiguous int64 rows vector, one entry per compact row")
+    dst = torch.empty((full_rows, cols), dtype=src.dtype, device=src.device)
+    call("rows_scatter", _ptr(src), _ptr(rows), _ptr(dst), n, full_rows, cols, _dt(src), _stream())
+    return dst
 
 
 def layernorm_fwd(x, w, b, eps: float):

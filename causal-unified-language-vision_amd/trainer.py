@@ -125,6 +125,10 @@ class DefaultTrainer:
 
     def init_train(self):
         self.model = self.pipeline.initialize_model()
+        # the training step reads the loss only: head and last MLP run on the rows with a label
+        # (batches that carry num_supervised). CULLAVO_SUPERVISED_ROWS=0 keeps the full path for A/B.
+        cm = self.model.cullavo_model if hasattr(self.model, "cullavo_model") else self.model
+        cm.supervised_rows = os.environ.get("CULLAVO_SUPERVISED_ROWS", "1") != "0"
         self.train_dataloaders = self.pipeline.get_dataloaders(self, "train", is_evaluation=False)
         self.create_optimizer_and_scheduler()
         self._initialize_accelerator()

@@ -55,8 +55,9 @@ extern "C" {
    cullavo_nf4_dequantize, cullavo_nf4_decode_linear added; 6: the switches of the measured-slower
    attention and GEMV variants removed with them: the attention backward's staging setter, the
    decode GEMV's non-temporal-load setter, and the retired values of cullavo_attn_set_stage /
-   cullavo_attn_set_bwd_tiles). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
-#define CULLAVO_ABI_VERSION 6
+   cullavo_attn_set_bwd_tiles; 7: the supervised-row entry points cullavo_rmsnorm_fwd_rows,
+   cullavo_rmsnorm_bwd_rows and cullavo_rows_scatter added). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
+#define CULLAVO_ABI_VERSION 7
 
 int cullavo_abi_version(void);
 const char* cullavo_last_error(void);
@@ -222,6 +223,33 @@ int cullavo_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int6
 int cullavo_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, void* dx,
                         const void* dres, void* dw, int w_dtype, float beta, float* workspace,
                         int64_t rows, int64_t cols, int dtype, void* stream);
+/* Supervised-row forms (ABI 7), for a training step that only needs the rows carrying a label.
+ * rows_idx [n] int64: ascending row indices into the full-height tensor, then padding entries of
+ * -1 at the tail (n counts both; the caller pads n to what its GEMMs need).
+ * cullavo_rmsnorm_fwd_rows: gather + norm in one pass. Compact row i is cullavo_rmsnorm_fwd's result
+ * for x[rows_idx[i]] (bitwise: the same kernel); x_rows (nullable) [n, cols] also receives the
+ * gathered input rows. A padding row is written as zeros (y, x_rows) with rstd 0. */
+int cullavo_rmsnorm_fwd_rows(const void* x, const int64_t* rows_idx, const void* w, void* y,
+                             float* rstd, void* x_rows, int64_t n, int64_t cols, float eps, int dtype,
+                             void* stream);
+/* cullavo_rmsnorm_bwd_rows: cullavo_rmsnorm_bwd over the compact dy, x, rstd and dres (nullable)
+ * [n, cols] with dx scattered to dx_full [full_rows, cols]: row rows_idx[i] gets compact row i's dx
+ * (bitwise cullavo_rmsnorm_bwd's), every other row exactly zero, or dres_full's row when dres_full
+ * [full_rows, cols] is given (nullable). compact_out != 0: dx_full is [n, cols] instead and gets
+ * compact row i's dx in row i (padding rows are not written; dres_full must be null). Padding rows
+ * are skipped. The kernels walk the full_rows rows in cullavo_rmsnorm_bwd's order and skip those
+ * without a compact row, so dw is bitwise what cullavo_rmsnorm_bwd gives on the full-height tensors
+ * whose other rows have dy = 0 (n = 0 writes beta * dw). */
+int cullavo_rmsnorm_bwd_rows(const void* dy, const void* x, const void* w, const float* rstd,
+                             const void* dres, const int64_t* rows_idx, void* dx_full,
+                             const void* dres_full, int64_t full_rows, int compact_out, void* dw,
+                             int w_dtype, float beta, float* workspace, int64_t n, int64_t cols,
+                             int dtype, void* stream);
+/* cullavo_rows_scatter: dst [full_rows, cols] gets src's [n, cols] compact row i in row rows_idx[i]
+ * and exact zeros in every other row (cols % 8 == 0). The weight-gradient GEMMs of the supervised-row
+ * tail read such operands: at full height they keep the full path's K order, bitwise. */
+int cullavo_rows_scatter(const void* src, const int64_t* rows_idx, void* dst, int64_t n,
+                         int64_t full_rows, int64_t cols, int dtype, void* stream);
 /* A/B switch for the bf16/f32 RMSNorm backward with dw at <= 4096 columns: 1 (default) = the
    pipelined one-workgroup-per-CU kernel (next rows' loads in flight under the current rows), 0 = the
    round-1 kernel (two waves per row). Both are deterministic; they add a row's dot-product
