@@ -40,6 +40,14 @@ class CullavoCausalLMOutputWithPast:
         return tuple(getattr(self, f.name) for f in fields(self) if getattr(self, f.name) is not None)
 
 
+@dataclass
+class CullavoGenerateOutput:
+    """generate(return_dict_in_generate=True): HF's GenerateDecoderOnlyOutput names. As there, the
+    cache holds every token of `sequences` but the last sampled one."""
+    sequences: torch.Tensor = None
+    past_key_values: object = None
+
+
 class CuLLaVOModel(nn.Module):
     def __init__(self, config: CuLLaVOConfig, *, device="cuda", trainable: str = "full", init: str = "random",
                  seed: int = 0, lora: LoraSettings | None = None, dtype=torch.bfloat16):
@@ -70,6 +78,8 @@ class CuLLaVOModel(nn.Module):
         # the trainer's opt-in to the supervised-row tail (forward's num_supervised); off, every caller
         # gets the full logits
         self.supervised_rows = False
+        # rows per piece of a cached forward's prefill (None: one pass; generate(prefill_chunk=N))
+        self.prefill_chunk = None
 
     @classmethod
     def from_pretrained(cls, path: str, *, device="cuda", trainable: str = "full", lora: LoraSettings | None = None,
@@ -258,7 +268,8 @@ class CuLLaVOModel(nn.Module):
 
     # -- KV-cache inference (reference :605-636 and HF generate; generation.py) ------------------
     def _forward_cached(self, input_ids, pixel_values, attention_mask, position_ids, cache, inputs_embeds,
-                        vision_feature_layer, strategy, labels, return_dict, max_len: int | None = None):
+                        vision_feature_layer, strategy, labels, return_dict, max_len: int | None = None,
+                        prefill_chunk: int | None = None):
         from .generation import KVCache, lm_infer
         if cache is not None and not isinstance(cache, KVCache):
             # transformers-layout cache (legacy tuple / DynamicCache, as the reference's decode branch
@@ -270,7 +281,7 @@ class CuLLaVOModel(nn.Module):
             try:
                 return self._forward_cached(input_ids, pixel_values, attention_mask, position_ids, cache,
                                             inputs_embeds, vision_feature_layer, strategy, labels, return_dict,
-                                            max_len)
+                                            max_len, prefill_chunk)
             finally:
                 torch.set_grad_enabled(True)
         self.vision_tower.eval()
@@ -284,7 +295,8 @@ class CuLLaVOModel(nn.Module):
         B, L = inputs_embeds.shape[:2]
         if max_len is None:
             max_len = L + 256
-        logits, cache = lm_infer(self.language_model, inputs_embeds, attention_mask, position_ids, cache, max_len)
+        logits, cache = lm_infer(self.language_model, inputs_embeds, attention_mask, position_ids, cache, max_len,
+                                 prefill_chunk if prefill_chunk is not None else self.prefill_chunk)
         out = CullavoCausalLMOutputWithPast(loss=None, logits=logits, past_key_values=cache, hidden_states=None,
                                             attentions=None)
         return out if return_dict else out.to_tuple()
@@ -293,10 +305,16 @@ class CuLLaVOModel(nn.Module):
     def generate(self, input_ids=None, pixel_values=None, attention_mask=None, max_new_tokens: int = 20,
                  do_sample: bool = False, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
                  eos_token_id: int | None = None, pad_token_id: int | None = None, use_cache: bool = True,
-                 generator=None, **kw):
+                 generator=None, past_key_values=None, return_dict_in_generate: bool = False,
+                 prefill_chunk: int | None = None, **kw):
         """Decoder-only generate: returns [B, S + new] (prompt ids then sampled ids), stopping when
-        every sequence has produced eos_token_id (finished rows are padded with pad_token_id)."""
-        from .generation import sample_next
+        every sequence has produced eos_token_id (finished rows are padded with pad_token_id).
+        past_key_values: the cache of an earlier call continues a conversation -- input_ids then holds
+        only the new turn (no pixel values; HF's convention: its first id is the last token the earlier
+        call sampled, which is not in the cache). return_dict_in_generate: a CullavoGenerateOutput
+        (.sequences, .past_key_values) instead of the ids. prefill_chunk: prefill the merged prompt in
+        pieces of at most that many rows (None: one pass)."""
+        from .generation import KVCache, sample_next
         if not use_cache:
             raise NotImplementedError("generate() runs on the KV cache (use_cache=True)")
         for ar in self.arenas.values():  # pending optimizer updates (FusedAdamW overlap)
@@ -311,10 +329,24 @@ class CuLLaVOModel(nn.Module):
         # image feature rows per <image> token: the patches, plus CLS under "full" (:588-597)
         n_feat = cfg.vision_config.num_patches + (1 if strategy == "full" else 0)
         L0 = S + n_img * (n_feat - 1)
-        out = self._forward_cached(input_ids, pixel_values, attention_mask, None, None, None,
-                                   cfg.vision_feature_layer, strategy, None, True,
-                                   max_len=L0 + max_new_tokens)
+        if past_key_values is None:
+            out = self._forward_cached(input_ids, pixel_values, attention_mask, None, None, None,
+                                       cfg.vision_feature_layer, strategy, None, True,
+                                       max_len=L0 + max_new_tokens, prefill_chunk=prefill_chunk)
+        else:
+            if pixel_values is not None:
+                raise NotImplementedError("generate(past_key_values=...) continues with text only: the images "
+                                          "are in the cache")
+            cache = past_key_values
+            if not isinstance(cache, KVCache):
+                cache = KVCache.from_legacy(cache, attention_mask)
+            # room for the new turn and every new token before the decode graph captures the cache
+            cache.grow(cache.length + S + max_new_tokens)
+            out = self._forward_cached(input_ids, None, attention_mask, None, cache, None, cfg.vision_feature_layer,
+                                       strategy, None, True, prefill_chunk=prefill_chunk)
         cache = out.past_key_values
+        if return_dict_in_generate:  # the cache's state before the first sampled token
+            len0, pos0 = cache.length, cache.next_pos.clone()
         logits = out.logits[:, -1]
         finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
         new = []
@@ -349,7 +381,14 @@ class CuLLaVOModel(nn.Module):
             all_done = done.all(0)
             if bool(all_done.any()):
                 gen = gen[:, :int(all_done.to(torch.int64).argmax()) + 1]
-        return torch.cat([input_ids, gen.to(input_ids.dtype)], 1)
+        sequences = torch.cat([input_ids, gen.to(input_ids.dtype)], 1)
+        if return_dict_in_generate:
+            # every returned token but the last is cached (rows a stopped batch ran past are dropped;
+            # the positions leave the decode graph's buffer)
+            fed = gen.shape[1] - 1
+            cache.length, cache.next_pos = len0 + fed, pos0 + fed
+            return CullavoGenerateOutput(sequences=sequences, past_key_values=cache)
+        return sequences
 
     # -- pieces ---------------------------------------------------------------------------------
     def _image_features(self, pixel_values, layer: int, strategy: str):

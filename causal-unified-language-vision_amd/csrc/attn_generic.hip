@@ -32,7 +32,11 @@ DEV bool visible(int64_t qg, int64_t jg, int Lk, int ks, bool causal) {
 
 // ---- forward -----------------------------------------------------------------------------------
 // thread t: query row r = t >> 2, keys j = part + 4 i (i < 16), output columns part + 4 c
-template <typename T, int D>
+// CACHED (cullavo_attn_fwd_cached; causal): the Lq queries are the last Lq positions of Lk = past +
+// Lq keys (query i sees keys <= past + i), K / V are one layer's KV cache, both with token stride
+// ldk, sequence b at element offset b * ldv (ldv carries the cache's batch stride); rows >= Lk of
+// the cache are never staged. lse may then be null.
+template <typename T, int D, bool CACHED>
 __global__ __launch_bounds__(256) void attn_gen_fwd_k(const T* __restrict__ Q, int64_t ldq, const T* __restrict__ K,
                                                       int64_t ldk, const T* __restrict__ V, int64_t ldv,
                                                       T* __restrict__ O, int64_t ldo, float* __restrict__ LSE, int H,
@@ -50,16 +54,23 @@ __global__ __launch_bounds__(256) void attn_gen_fwd_k(const T* __restrict__ Q, i
   const int t = threadIdx.x, r = t >> 2, part = t & 3;
   const int ks = kv_start ? kv_start[b] : 0;
   const int64_t qg = q0 + r;
+  const int past = CACHED ? Lk - Lq : 0;
+  const int64_t qpos = past + qg;  // the query's key position
+  // sequence b's first K / V row: row b * Lk of the packed [B * Lk] rows, or of its own cache
+  const T* Kb = K + (CACHED ? (int64_t)b * ldv : 0) + h * D;
+  const T* Vb = V + (CACHED ? (int64_t)b * ldv : 0) + h * D;
+  const int64_t krow0 = CACHED ? 0 : (int64_t)b * Lk;
+  const int64_t ldvt = CACHED ? ldk : ldv;
   stage_rows<T>(sQ, LD, Q + h * D, ldq, (int64_t)b * Lq + q0, min(QF, Lq - q0), QF, D);
   float m = -INFINITY, l = 0.f;
   float o[D / 4];
 #pragma unroll
   for (int c = 0; c < D / 4; ++c) o[c] = 0.f;
-  const int kend = causal ? min(Lk, q0 + QF) : Lk;
+  const int kend = causal ? min(Lk, past + q0 + QF) : Lk;
   for (int k0 = 0; k0 < kend; k0 += KB) {
     __syncthreads();
-    stage_rows<T>(sK, LD, K + h * D, ldk, (int64_t)b * Lk + k0, min(KB, Lk - k0), KB, D);
-    stage_rows<T>(sV, LD, V + h * D, ldv, (int64_t)b * Lk + k0, min(KB, Lk - k0), KB, D);
+    stage_rows<T>(sK, LD, Kb, ldk, krow0 + k0, min(KB, Lk - k0), KB, D);
+    stage_rows<T>(sV, LD, Vb, ldvt, krow0 + k0, min(KB, Lk - k0), KB, D);
     __syncthreads();
     float s[KB / 4];
     float bmax = -INFINITY;
@@ -68,7 +79,7 @@ __global__ __launch_bounds__(256) void attn_gen_fwd_k(const T* __restrict__ Q, i
       const int j = part + 4 * i;
       float acc = 0.f;
       for (int d = 0; d < D; ++d) acc = fmaf(sQ[r * LD + d], sK[j * LD + d], acc);
-      s[i] = visible(qg, k0 + j, Lk, ks, causal) && qg < Lq ? acc * scale : -INFINITY;
+      s[i] = visible(qpos, k0 + j, Lk, ks, causal) && qg < Lq ? acc * scale : -INFINITY;
       bmax = fmaxf(bmax, s[i]);
     }
     bmax = fmaxf(bmax, __shfl_xor(bmax, 1, 64));
@@ -100,7 +111,8 @@ __global__ __launch_bounds__(256) void attn_gen_fwd_k(const T* __restrict__ Q, i
     T* op = O + ((int64_t)b * Lq + qg) * ldo + h * D;
 #pragma unroll
     for (int c = 0; c < D / 4; ++c) Elt<T>::st(op, part + 4 * c, o[c] * inv);
-    if (part == 0) LSE[((int64_t)b * H + h) * Lq + qg] = l > 0.f ? m + __logf(l) : INFINITY;
+    if ((!CACHED || LSE != nullptr) && part == 0)
+      LSE[((int64_t)b * H + h) * Lq + qg] = l > 0.f ? m + __logf(l) : INFINITY;
   }
 }
 
@@ -271,13 +283,32 @@ int gen_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* 
   const int smem = (QF * LD + 2 * KB * LD + QF * (KB + 1)) * 4;
   static bool once = false;
   if (!once) {
-    (void)hipFuncSetAttribute((const void*)attn_gen_fwd_k<T, D>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    (void)hipFuncSetAttribute((const void*)attn_gen_fwd_k<T, D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     once = true;
   }
   const unsigned grid = (unsigned)(cdiv(Lq, QF) * H * B);
-  attn_gen_fwd_k<T, D><<<grid, 256, smem, s>>>((const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, (T*)o, ldo, lse,
+  attn_gen_fwd_k<T, D, false><<<grid, 256, smem, s>>>((const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, (T*)o, ldo, lse,
                                                H, Lq, Lk, scale, causal, ks);
   return cullavo_check_launch("attn_fwd (generic)");
+}
+
+template <typename T, int D>
+int gen_fwd_cached(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ld_tok, int64_t ld_batch,
+                   void* o, int64_t ldo, float* lse, int B, int H, int Lq, int past, float scale, const int32_t* ks,
+                   hipStream_t s) {
+  constexpr int LD = D + 1;
+  const int smem = (QF * LD + 2 * KB * LD + QF * (KB + 1)) * 4;
+  static bool once = false;
+  if (!once) {
+    (void)hipFuncSetAttribute((const void*)attn_gen_fwd_k<T, D, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              smem);
+    once = true;
+  }
+  const unsigned grid = (unsigned)(cdiv(Lq, QF) * H * B);
+  // (K, its token stride, V, the batch stride: see the kernel's CACHED note)
+  attn_gen_fwd_k<T, D, true><<<grid, 256, smem, s>>>((const T*)q, ldq, (const T*)kc, ld_tok, (const T*)vc, ld_batch,
+                                                     (T*)o, ldo, lse, H, Lq, past + Lq, scale, 1, ks);
+  return cullavo_check_launch("attn_fwd_cached (generic)");
 }
 
 template <typename T, int D>
@@ -326,6 +357,28 @@ int cullavo_attn_generic_fwd(const void* q, int64_t ldq, const void* k, int64_t 
   else { GFD(u16) }
 #undef GFD
 #undef GF
+  cullavo_set_error("attention: head_dim must be 16, 32, 64 or 128");
+  return CULLAVO_EUNSUPPORTED;
+}
+
+// Dispatch used by cullavo_attn_fwd_cached (attention.hip) for f32 storage or D in {16, 32}.
+int cullavo_attn_generic_fwd_cached(const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
+                                    int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B, int H,
+                                    int Lq, int past, int D, float scale, const int32_t* ks, int dtype, hipStream_t s) {
+#define GC(T_, D_) \
+  return gen_fwd_cached<T_, D_>(q, ldq, k_cache, v_cache, ld_tok, ld_batch, o, ldo, lse, B, H, Lq, past, scale, ks, s)
+#define GCD(T_)                  \
+  switch (D) {                   \
+    case 16: GC(T_, 16);         \
+    case 32: GC(T_, 32);         \
+    case 64: GC(T_, 64);         \
+    case 128: GC(T_, 128);       \
+    default: break;              \
+  }
+  if (dtype == CULLAVO_DT_F32) { GCD(float) }
+  else { GCD(u16) }
+#undef GCD
+#undef GC
   cullavo_set_error("attention: head_dim must be 16, 32, 64 or 128");
   return CULLAVO_EUNSUPPORTED;
 }

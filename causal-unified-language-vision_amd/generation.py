@@ -10,7 +10,12 @@ MI355X design: the cache is preallocated once per generate() call in HBM as K, V
 [layers, B, Lmax, H*D] bf16; the prompt (text + 576 image rows, merged exactly as training
 does) is prefilled through the same fused kernels (GEMMs, RoPE, causal flash attention) with
 its rotated keys/values appended by kv_append; every decode step runs the layers on one row
-per sequence and attends with the split-KV attn_decode kernel. Left-padded batches are
+per sequence and attends with the split-KV attn_decode kernel. A cached step may also carry
+several new tokens per sequence -- a follow-up turn, a second question about an image whose rows
+are already cached, the later pieces of a chunked prefill (generate(prefill_chunk=N)): RoPE at
+next_pos .. next_pos + n - 1, kv_append, then attn_fwd_cached, the causal flash kernel with a
+query offset over the cache's first length + n rows (reference: any number of new input_ids with
+past_key_values, arch_cullavo.py:605-647). Its new tokens must all be attended. Left-padded batches are
 supported through kv_start (keys before the first attended token are masked); a prompt with
 holes in its attention mask is not (decode attention reads one contiguous key range).
 Sampling (temperature, top-k, top-p, multinomial; or greedy) follows HF's warper order on the
@@ -141,7 +146,8 @@ def _nf4_linear(q, x, w, group, residual=None):
 def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int, start, kv_len,
                 attn_len: int | None = None):
     """One LlamaDecoderLayer over Lnew new rows per sequence (prefill: Lnew = prompt length on an
-    empty cache; decode: Lnew = 1), appending their keys/values to the cache. No autograd.
+    empty cache; decode: Lnew = 1; continuation: Lnew > 1 on a filled cache, attending the cached
+    prefix through ops.attn_fwd_cached), appending their keys/values to the cache. No autograd.
     attn_len: the key range decode attention is sized for (default: the filled rows + 1)."""
     cfg = layer.cfg
     d, H, D = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim
@@ -181,7 +187,12 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int,
     else:
         ops.rope(q, k, sctx.position_ids, hq=H, hk=H, head_dim=D, theta=cfg.rope_theta)
         ops.kv_append(k, v, cache.k[li], cache.v[li], start, B=B, Lnew=Lnew)
-    if Lnew > 1:
+    if Lnew > 1 and cache.length > 0:
+        # continuation: the new rows against the cached prefix and themselves (their keys / values
+        # were appended just above), causal from the row's own position
+        o, _ = ops.attn_fwd_cached(q, cache.k[li], cache.v[li], B=B, H=H, Lq=Lnew, past=cache.length, D=D,
+                                   scale=D ** -0.5, kv_start=sctx.kv_start)
+    elif Lnew > 1:
         o, _ = ops.attn_fwd(q, k, v, B=B, H=H, Lq=Lnew, Lk=Lnew, D=D, scale=D ** -0.5, causal=True,
                             kv_start=sctx.kv_start)
     elif not (qkv.dtype == torch.bfloat16 and FUSE_DECODE_ROPE):
@@ -281,9 +292,30 @@ class DecodeGraph:
         return self.logits
 
 
-def lm_infer(lm, embeds, attention_mask, position_ids, cache: KVCache | None, max_len: int):
-    """LlamaForCausalLM with a KV cache: prefill (cache None or empty) or one decode step.
-    Returns (logits [B, Lnew, V] bf16, cache)."""
+def _infer_rows(lm, embeds, position_ids, cache: KVCache):
+    """The decoder layers, final norm and lm_head over embeds [B, Lnew, d], appended to the cache at
+    cache.length; returns logits [B, Lnew, V]."""
+    B, Lnew, d = embeds.shape
+    cfg = lm.cfg
+    sctx = StepContext(B, Lnew, position_ids, cache.kv_start, lora_seed=0)
+    h = embeds.reshape(B * Lnew, d).contiguous()
+    start = torch.full((B,), cache.length, dtype=torch.int32, device=h.device)
+    kv_len = start + Lnew
+    for li, layer in enumerate(lm.model.layers):
+        h = layer_infer(layer, h, sctx, cache, li, Lnew, start, kv_len)
+    cache.length += Lnew
+    x, _ = ops.rmsnorm_fwd(h, lm.model.norm.weight, cfg.rms_norm_eps)
+    logits = ops.linear(x, lm.lm_head.weight)
+    return logits.view(B, Lnew, -1)
+
+
+def lm_infer(lm, embeds, attention_mask, position_ids, cache: KVCache | None, max_len: int,
+             prefill_chunk: int | None = None):
+    """LlamaForCausalLM with a KV cache: prefill (cache None or empty), one decode step, or a
+    continuation of Lnew > 1 new tokens per sequence on a filled cache (a follow-up turn, a second
+    question about the cached image, the later pieces of a chunked prefill). prefill_chunk: run the
+    rows in pieces of at most that many per sequence (None: one pass). Returns (logits [B, Lnew, V]
+    bf16, cache)."""
     B, Lnew, d = embeds.shape
     cfg = lm.cfg
     if embeds.dtype != torch.bfloat16:
@@ -306,24 +338,36 @@ def lm_infer(lm, embeds, attention_mask, position_ids, cache: KVCache | None, ma
         if position_ids is None:
             position_ids = (am.cumsum(-1) - 1).masked_fill(am == 0, 1)
         cache.next_pos = position_ids[:, -1].to(torch.int64) + 1
-    else:
-        if Lnew != 1:
-            raise NotImplementedError("after the prefill, cached steps take one token per sequence")
+    elif Lnew == 1:
         if cache.length + 1 > cache.max_len:  # room for 256 more steps (one copy per 256 steps)
             cache.grow(cache.max_len + 256)
         if position_ids is None:
             position_ids = cache.next_pos[:, None]
         cache.next_pos = cache.next_pos + 1
-    sctx = StepContext(B, Lnew, position_ids, cache.kv_start, lora_seed=0)
-    h = embeds.reshape(B * Lnew, d).contiguous()
-    start = torch.full((B,), cache.length, dtype=torch.int32, device=h.device)
-    kv_len = start + Lnew
-    for li, layer in enumerate(lm.model.layers):
-        h = layer_infer(layer, h, sctx, cache, li, Lnew, start, kv_len)
-    cache.length += Lnew
-    x, _ = ops.rmsnorm_fwd(h, lm.model.norm.weight, cfg.rms_norm_eps)
-    logits = ops.linear(x, lm.lm_head.weight)
-    return logits.view(B, Lnew, -1), cache
+    else:
+        if attention_mask is not None:
+            # a 2-D mask ending in the new tokens (past + new rows, or the new ones alone): the cached
+            # part is the cache's own state (kv_start); the new tokens must all be attended (the
+            # kernels read one contiguous key range)
+            if attention_mask.dim() != 2 or attention_mask.shape[1] < Lnew:
+                raise ValueError(f"attention_mask {tuple(attention_mask.shape)}: expected [B, >= {Lnew}]")
+            if bool((attention_mask[:, -Lnew:] == 0).any()):
+                raise NotImplementedError("a continuation chunk with masked tokens (every new token of a cached "
+                                          "step must be attended)")
+        if cache.length + Lnew > cache.max_len:  # in 256-row steps, as the decode steps grow it
+            cache.grow(cache.max_len + 256 * -(-(cache.length + Lnew - cache.max_len) // 256))
+        if position_ids is None:
+            position_ids = cache.next_pos[:, None] + torch.arange(Lnew, device=embeds.device)
+        cache.next_pos = cache.next_pos + Lnew
+    if prefill_chunk is not None and Lnew > prefill_chunk:
+        if prefill_chunk < 1:
+            raise ValueError(f"prefill_chunk must be positive, got {prefill_chunk}")
+        # pieces of at most prefill_chunk rows: the first on the empty cache as a plain prefill, the
+        # others as continuations (kv_start masks a sequence's left padding in every piece)
+        logits = [_infer_rows(lm, embeds[:, c:c + prefill_chunk], position_ids[:, c:c + prefill_chunk], cache)
+                  for c in range(0, Lnew, prefill_chunk)]
+        return torch.cat(logits, 1), cache
+    return _infer_rows(lm, embeds, position_ids, cache), cache
 
 
 def sample_next(logits, *, do_sample: bool, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,

@@ -19,7 +19,7 @@ __all__ = [
     "ACT_NONE", "ACT_GELU", "ACT_QUICK_GELU", "ACT_SWIGLU_BWD", "gemm", "gemm_ex", "linear", "linear_dx", "linear_dx_t", "transpose2d", "linear_dw",
     "rmsnorm_fwd", "rmsnorm_bwd", "supervised_rows", "gather_targets", "rmsnorm_fwd_rows", "rmsnorm_bwd_rows", "rows_scatter",
     "layernorm_fwd", "layernorm_bwd", "swiglu_fwd", "swiglu_bwd",
-    "act_bwd", "colsum", "rope", "attn_fwd", "attn_bwd", "embedding_fwd", "embedding_bwd",
+    "act_bwd", "colsum", "rope", "attn_fwd", "attn_fwd_cached", "attn_bwd", "embedding_fwd", "embedding_bwd",
     "im2col_patches", "vision_embed_ln", "merge_plan", "row_gather2", "shift_targets", "ce_fwd",
     "ce_reduce", "ce_bwd", "adamw", "sumsq", "clip_coef", "scale_inplace", "kv_append", "attn_decode",
     "clip_image_preprocess", "visimage_geometry", "draw_boxes",
@@ -624,6 +624,21 @@ def attn_decode(q, k_cache, v_cache, kv_len, *, B: int, H: int, D: int, max_len:
     call("attn_decode", _ptr(q), _ld(q), _ptr(k_cache), _ptr(v_cache), k_cache.stride(1), k_cache.stride(0),
          _ptr(kv_len), _ptr(kv_start), _ptr(o), _ld(o), B, H, max_len, D, float(scale), _ptr(ws), _stream())
     return o
+
+
+def attn_fwd_cached(q, k_cache, v_cache, *, B: int, H: int, Lq: int, past: int, D: int, scale: float,
+                    kv_start=None, out=None):
+    """cullavo_attn_fwd_cached: Lq new rows per sequence (q [B*Lq, >=H*D]) against the first past + Lq
+    rows of one layer's caches [B, Lmax, H*D], whose rows past .. past+Lq-1 already hold the new keys /
+    values; query i attends keys kv_start[b] <= j <= past + i. Returns (o [B*Lq, H*D], lse [B,H,Lq] f32)."""
+    _dev(q, k_cache, v_cache, kv_start)
+    if k_cache.dim() != 3 or k_cache.stride(2) != 1 or v_cache.stride() != k_cache.stride():
+        raise ValueError("expected caches [B, Lmax, H*D] with unit column stride and the same strides")
+    o = out if out is not None else torch.empty((B * Lq, H * D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+    call("attn_fwd_cached", _ptr(q), _ld(q), _ptr(k_cache), _ptr(v_cache), k_cache.stride(1), k_cache.stride(0),
+         _ptr(o), _ld(o), _ptr(lse), B, H, Lq, past, D, float(scale), _ptr(kv_start), _dt(q), _stream())
+    return o, lse
 
 
 def attn_bwd(q, k, v, o, do, lse, *, B: int, H: int, Lq: int, Lk: int, D: int, scale: float, causal: bool,

@@ -56,8 +56,8 @@ extern "C" {
    attention and GEMV variants removed with them: the attention backward's staging setter, the
    decode GEMV's non-temporal-load setter, and the retired values of cullavo_attn_set_stage /
    cullavo_attn_set_bwd_tiles; 7: the supervised-row entry points cullavo_rmsnorm_fwd_rows,
-   cullavo_rmsnorm_bwd_rows and cullavo_rows_scatter added). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
-#define CULLAVO_ABI_VERSION 7
+   cullavo_rmsnorm_bwd_rows and cullavo_rows_scatter added; 8: cullavo_attn_fwd_cached added). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
+#define CULLAVO_ABI_VERSION 8
 
 int cullavo_abi_version(void);
 const char* cullavo_last_error(void);
@@ -380,6 +380,27 @@ int cullavo_attn_decode_rope(const void* q, int64_t ldq, const void* k, int64_t 
 int cullavo_kv_append(const void* k, int64_t ldk, const void* v, int64_t ldv, void* k_cache, void* v_cache,
                       int64_t ld_tok, int64_t ld_batch, const int32_t* start, int B, int Lnew, int64_t hd,
                       void* stream);
+/* Several new tokens per sequence against a KV-cache prefix (ABI 8, additive): the attention of the
+ * reference's cached forward with any number of new input_ids -- past_key_values handed to the HF
+ * Llama model (cullavo/arch_cullavo.py:605-647), whose attention concatenates the cached keys with
+ * the new ones and applies the causal mask aligned bottom-right (tf:llama/modeling_llama.py cached
+ * branch; FA2's causal convention for Lq < Lk). A second question about an image, a follow-up turn
+ * and a chunked prefill are this call.
+ * q, o: [B*Lq, >= H*D], the new rows (token strides ldq, ldo). k_cache, v_cache: one layer's
+ * [B, Lmax, H*D] (token stride ld_tok, batch stride ld_batch) whose rows past .. past+Lq-1 already
+ * hold the new keys / values (call order: cullavo_rope, cullavo_kv_append, this). Query i of
+ * sequence b attends keys kv_start[b] <= j <= past + i (kv_start nullable: 0); with Lk = past + Lq
+ * that is causal attention whose queries are the last Lq positions. Cache rows >= past + Lq are
+ * never read into a result, whatever they hold. A query with no visible key returns a zero row and
+ * lse = +inf. lse: nullable, [B, H, Lq] f32 natural log. past = 0 is cullavo_attn_fwd(causal = 1,
+ * Lq == Lk) bit for bit. bf16 with D in {64, 128}: the pipelined MFMA forward with a query offset
+ * and a K/V batch stride of its own (128-query and 64-key tiles, the LDS-DMA bound of a sequence
+ * set to its past + Lq rows); f32 and D < 64: the generic kernel. Errors (CULLAVO_EINVAL) as
+ * cullavo_attn_fwd, and past < 0 or ld_batch < (past + Lq) * ld_tok. */
+int cullavo_attn_fwd_cached(const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
+                            int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B,
+                            int H, int Lq, int past, int D, float scale, const int32_t* kv_start,
+                            int dtype, void* stream);
 /* Decode-step Linear over M <= 16 rows (one token per sequence; reference: the cached forward's
  * decoder layer, cullavo/arch_cullavo.py:605-636) with its input transform fused into the weight
  * stream (csrc/gemv.hip): y[M,N] = X W^T (+ residual), W [N,K] bf16 (ldw), where X is

@@ -22,6 +22,41 @@ def timeit(fn, iters=10):
     return s.elapsed_time(e) / iters
 
 
+def cached_cases():
+    """--cached: ops.attn_fwd_cached (Lq new queries on a 1088-row cache prefix, the config-3 prompt)
+    next to ops.attn_fwd causal at Lq = Lk = past + Lq, which computes a superset of the same
+    products; the two alternate (three rounds), and the cached rows are compared with the full
+    pass's last Lq rows. Algorithmic FLOPs of the cached call: 4 B H D (Lq past + Lq (Lq + 1) / 2)."""
+    H, D, past = 32, 128, 1088
+    for B in (1, 8):
+        for Lq in (16, 64, 512):
+            L = past + Lq
+            torch.manual_seed(0)
+            qkv = (torch.randn(B * L, 3 * H * D, device="cuda") * 0.5).bfloat16()
+            q, k, v = qkv[:, :H * D], qkv[:, H * D:2 * H * D], qkv[:, 2 * H * D:]
+            kc = k.reshape(B, L, H * D).contiguous()
+            vc = v.reshape(B, L, H * D).contiguous()
+            qn = q.reshape(B, L, H * D)[:, past:].reshape(B * Lq, H * D).contiguous()
+            kw = dict(B=B, H=H, D=D, scale=D ** -0.5)
+            full = lambda: ops.attn_fwd(q, k, v, Lq=L, Lk=L, causal=True, **kw)
+            cached = lambda: ops.attn_fwd_cached(qn, kc, vc, Lq=Lq, past=past, **kw)
+            o_full = full()[0].reshape(B, L, H * D)[:, past:].reshape(B * Lq, H * D).float()
+            o_c = cached()[0].float()
+            rel = ((o_c - o_full).norm() / o_full.norm()).item()
+            tc, tf = [], []
+            for _ in range(3):
+                tc.append(timeit(cached, iters=200))
+                tf.append(timeit(full, iters=50))
+            fl = 4.0 * B * H * D * (Lq * past + Lq * (Lq + 1) / 2)
+            print(f"cached B {B} H {H} D {D} past {past} Lq {Lq:4d}: attn_fwd_cached "
+                  + " ".join(f"{t * 1e3:7.1f}" for t in tc) + f" us ({fl / min(tc) / 1e9:6.1f} TF) | attn_fwd causal L {L} "
+                  + " ".join(f"{t * 1e3:7.1f}" for t in tf) + f" us | rel diff of the shared rows {rel:.1e}", flush=True)
+
+
+if "--cached" in sys.argv:
+    cached_cases()
+    sys.exit(0)
+
 STAGES = [int(x) for x in os.environ.get("ATTN_STAGE_AB", "7").split(",")]  # forward kernels, e.g. 4,7,4,7
 ref_out = {}
 for stage in STAGES:
