@@ -306,17 +306,25 @@ class CuLLaVOModel(nn.Module):
                  do_sample: bool = False, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
                  eos_token_id: int | None = None, pad_token_id: int | None = None, use_cache: bool = True,
                  generator=None, past_key_values=None, return_dict_in_generate: bool = False,
-                 prefill_chunk: int | None = None, **kw):
+                 prefill_chunk: int | None = None, seed: int | None = None, device_loop: bool | None = None, **kw):
         """Decoder-only generate: returns [B, S + new] (prompt ids then sampled ids), stopping when
         every sequence has produced eos_token_id (finished rows are padded with pad_token_id).
         past_key_values: the cache of an earlier call continues a conversation -- input_ids then holds
         only the new turn (no pixel values; HF's convention: its first id is the last token the earlier
         call sampled, which is not in the cache). return_dict_in_generate: a CullavoGenerateOutput
         (.sequences, .past_key_values) instead of the ids. prefill_chunk: prefill the merged prompt in
-        pieces of at most that many rows (None: one pass)."""
-        from .generation import KVCache, sample_next
+        pieces of at most that many rows (None: one pass).
+        seed / device_loop: the device loop (generation.SamplerState, the sampling kernel captured at
+        the end of the decode graph). seed=int samples with Philox streams keyed by (seed, the
+        sequence's stream id, the token's index): reproducible without a torch.Generator and, for a
+        sequence, independent of its batch neighbours; the stream ids default to arange(B) and
+        sample_offsets=<[B] ints> overrides them. device_loop=True alone decodes greedily on the
+        device. With neither argument the host loop around generation.sample_next runs unchanged."""
+        from .generation import KVCache, device_sampling, sample_next
         if not use_cache:
             raise NotImplementedError("generate() runs on the KV cache (use_cache=True)")
+        on_device = device_sampling(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                                    generator=generator, seed=seed, device_loop=device_loop)
         for ar in self.arenas.values():  # pending optimizer updates (FusedAdamW overlap)
             ar.wait_update()
         cfg = self.config
@@ -348,32 +356,36 @@ class CuLLaVOModel(nn.Module):
         if return_dict_in_generate:  # the cache's state before the first sampled token
             len0, pos0 = cache.length, cache.next_pos.clone()
         logits = out.logits[:, -1]
-        finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
-        new = []
-        # the decode steps replay one captured HIP graph (generation.DecodeGraph) unless asked not to
-        graph = None
-        if kw.get("decode_graph", True) and max_new_tokens > 1 and input_ids.is_cuda:
-            from .generation import DecodeGraph
-            graph = DecodeGraph(self, cache)
-        check_every = 16  # all-finished test every 16 tokens: one host sync per 16 steps, not per step
-        for step in range(max_new_tokens):
-            tok = sample_next(logits, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
-                              generator=generator)
-            tok = torch.where(finished, torch.full_like(tok, pad), tok)
-            new.append(tok)
-            if eos_token_id is not None:
-                finished |= tok == eos_token_id
-                if (step + 1) % check_every == 0 and bool(finished.all()):
+        if on_device:
+            gen = self._generate_on_device(cache, logits, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
+                                           eos_token_id, pad, kw)
+        else:
+            finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
+            new = []
+            # the decode steps replay one captured HIP graph (generation.DecodeGraph) unless asked not to
+            graph = None
+            if kw.get("decode_graph", True) and max_new_tokens > 1 and input_ids.is_cuda:
+                from .generation import DecodeGraph
+                graph = DecodeGraph(self, cache)
+            check_every = 16  # all-finished test every 16 tokens: one host sync per 16 steps, not per step
+            for step in range(max_new_tokens):
+                tok = sample_next(logits, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                                  generator=generator)
+                tok = torch.where(finished, torch.full_like(tok, pad), tok)
+                new.append(tok)
+                if eos_token_id is not None:
+                    finished |= tok == eos_token_id
+                    if (step + 1) % check_every == 0 and bool(finished.all()):
+                        break
+                if step + 1 == max_new_tokens:
                     break
-            if step + 1 == max_new_tokens:
-                break
-            if graph is not None:
-                logits = graph.step(tok)[:, -1]
-            else:
-                out = self._forward_cached(tok[:, None], None, None, None, cache, None, cfg.vision_feature_layer,
-                                           cfg.vision_feature_select_strategy, None, True)
-                logits = out.logits[:, -1]
-        gen = torch.stack(new, 1)
+                if graph is not None:
+                    logits = graph.step(tok)[:, -1]
+                else:
+                    out = self._forward_cached(tok[:, None], None, None, None, cache, None, cfg.vision_feature_layer,
+                                               cfg.vision_feature_select_strategy, None, True)
+                    logits = out.logits[:, -1]
+            gen = torch.stack(new, 1)
         if eos_token_id is not None:
             # HF stops at the first step where every row has finished; the steps run past it (at
             # most check_every - 1) hold only padding and are dropped
@@ -389,6 +401,35 @@ class CuLLaVOModel(nn.Module):
             cache.length, cache.next_pos = len0 + fed, pos0 + fed
             return CullavoGenerateOutput(sequences=sequences, past_key_values=cache)
         return sequences
+
+    def _generate_on_device(self, cache, logits, max_new_tokens: int, do_sample: bool, temperature, top_k, top_p,
+                            seed, eos_token_id, pad, kw):
+        """generate()'s device loop: the first token by the sampling kernel on the prefill logits,
+        every later one by a replay of the decode graph that ends with that kernel; the host reads
+        `finished` every 16 replays and the tokens once at the end. Returns the new ids [B, n]."""
+        from .generation import DecodeGraph, SamplerState
+        cfg = self.config
+        B = logits.shape[0]
+        state = SamplerState(B, max_new_tokens, logits.device, do_sample=do_sample, temperature=temperature,
+                             top_k=top_k, top_p=top_p, seed=seed if seed is not None else 0,
+                             eos_token_id=eos_token_id, pad_token_id=pad, row_offset=kw.get("sample_offsets"))
+        state.sample(logits)
+        graph = None
+        if kw.get("decode_graph", True) and max_new_tokens > 1:
+            graph = DecodeGraph(self, cache, sampler=state)
+        check_every = 16  # as the host loop: one host sync per 16 tokens
+        n = 1
+        while n < max_new_tokens:
+            if eos_token_id is not None and n % check_every == 0 and bool(state.finished.all()):
+                break
+            if graph is not None:
+                graph.advance()
+            else:
+                out = self._forward_cached(state.next_ids[:, None], None, None, None, cache, None,
+                                           cfg.vision_feature_layer, cfg.vision_feature_select_strategy, None, True)
+                state.sample(out.logits[:, -1])
+            n += 1
+        return state.out_tokens[:, :n].clone()
 
     # -- pieces ---------------------------------------------------------------------------------
     def _image_features(self, pixel_values, layer: int, strategy: str):

@@ -20,6 +20,13 @@ supported through kv_start (keys before the first attended token are masked); a 
 holes in its attention mask is not (decode attention reads one contiguous key range).
 Sampling (temperature, top-k, top-p, multinomial; or greedy) follows HF's warper order on the
 GPU with torch ops: it is O(B x vocab) per token and not a kernel of the hot path.
+generate(seed=...) / generate(device_loop=True) take the other route: one HIP kernel
+(csrc/sample.hip, ops.sample_token) does the warpers, a Philox draw seeded per sequence and the
+eos / pad bookkeeping, is captured at the end of the decode graph (DecodeGraph(sampler=...)) and
+writes the next step's input token on the device, so a generation is a row of graph replays with
+one host read of `finished` every 16 tokens. It takes 1 <= top_k <= 1024; top_k=0 (the nucleus
+over the full vocabulary), repetition penalties and beam search stay with the host loop or are
+not implemented.
 """
 from __future__ import annotations
 
@@ -225,6 +232,73 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int,
     return _nf4_linear(nf4.get("down"), a, layer.mlp.down_proj.weight, lg["down"], residual=h2)
 
 
+SAMPLE_TOP_K_MAX = 1024  # cullavo_sample_token: 1 <= top_k <= 1024
+
+
+def device_sampling(*, do_sample: bool, temperature: float, top_k: int, top_p: float, generator, seed,
+                    device_loop) -> bool:
+    """Whether generate() runs its device loop (the sampling kernel, captured into the decode graph)
+    or today's host loop around sample_next: the device loop runs when a seed is given (sampling) or
+    device_loop=True (greedy, or sampling with a seed); a call with neither runs the host loop.
+    Raises ValueError for the combinations neither loop serves."""
+    if seed is None and not device_loop:
+        return False
+    if seed is not None:
+        if generator is not None:
+            raise ValueError("generate(): seed= (the device loop's Philox streams) and generator= (the host loop's "
+                             "torch.Generator) exclude each other")
+        if not do_sample:
+            raise ValueError("generate(): seed= needs do_sample=True (greedy decoding draws nothing)")
+        if device_loop is not None and not device_loop:
+            raise ValueError("generate(): seed= runs the device loop; device_loop=False has no seeded sampling "
+                             "(pass generator= instead)")
+        if not isinstance(top_k, int) or not 1 <= top_k <= SAMPLE_TOP_K_MAX:
+            raise ValueError(f"generate(): seed= samples with the device kernel, which takes 1 <= top_k <= "
+                             f"{SAMPLE_TOP_K_MAX} (got {top_k}; top_k=0, the nucleus over the full vocabulary, runs "
+                             f"on the host loop with generator=)")
+        if not (temperature > 0 and temperature < float("inf")) or not 0 < top_p <= 1:
+            raise ValueError(f"generate(): temperature must be finite and > 0 and top_p in (0, 1] "
+                             f"(got {temperature}, {top_p})")
+    elif do_sample:
+        raise ValueError("generate(): device_loop=True with do_sample=True needs seed= (the device loop does not "
+                         "read a torch.Generator)")
+    if generator is not None:
+        raise ValueError("generate(): device_loop=True does not take generator=")
+    return True
+
+
+class SamplerState:
+    """The device state of one generation on the sampling kernel (ops.sample_token) and its
+    parameters: next_ids [B] (the token the next decode step embeds), step [B] (tokens produced, the
+    Philox counter), row_offset [B] (each sequence's stream id: with seed it fixes the sequence's
+    draws whatever the batch around it), finished [B] and out_tokens [B, max_new_tokens]."""
+
+    def __init__(self, B: int, max_new_tokens: int, device, *, do_sample: bool, temperature: float = 1.0,
+                 top_k: int = 50, top_p: float = 1.0, seed: int = 0, eos_token_id: int | None = None,
+                 pad_token_id: int = 0, row_offset=None):
+        self.next_ids = torch.zeros(B, dtype=torch.int64, device=device)
+        self.step = torch.zeros(B, dtype=torch.int64, device=device)
+        if row_offset is None:
+            self.row_offset = torch.arange(B, dtype=torch.int64, device=device)
+        else:
+            self.row_offset = torch.as_tensor(row_offset).to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+            if self.row_offset.numel() != B:
+                raise ValueError(f"sample_offsets: expected {B} stream ids, got {self.row_offset.numel()}")
+        self.finished = torch.zeros(B, dtype=torch.uint8, device=device)
+        self.out_tokens = torch.full((B, max_new_tokens), pad_token_id, dtype=torch.int64, device=device)
+        self.do_sample = bool(do_sample)
+        # greedy ignores the warpers; the kernel still validates them
+        self.temperature, self.top_k, self.top_p = (temperature, top_k, top_p) if do_sample else (1.0, 1, 1.0)
+        self.seed, self.eos_token_id, self.pad_token_id = int(seed), eos_token_id, int(pad_token_id)
+
+    def sample(self, logits):
+        """one token per row from logits [B, V] (bf16, a row-strided view): everything in place"""
+        ops.sample_token(logits, next_ids=self.next_ids, step=self.step, temperature=self.temperature,
+                         top_k=self.top_k, top_p=self.top_p, do_sample=self.do_sample, seed=self.seed,
+                         row_offset=self.row_offset, eos_id=self.eos_token_id, pad_id=self.pad_token_id,
+                         finished=self.finished, out_tokens=self.out_tokens)
+
+
 class DecodeGraph:
     """One cached decode step of the LM -- the new token's embedding row, every decoder layer at one
     row per sequence, the final norm and lm_head -- captured once as a HIP graph and replayed per
@@ -234,14 +308,18 @@ class DecodeGraph:
     RoPE positions and the cache write row (+1 at the end of every replay); decode attention runs
     over the cache's full capacity (chunks past a row's length exit at once), so the grid does not
     depend on the current length. The cache must not grow while the graph is alive (generate()
-    sizes it for prompt + max_new_tokens)."""
+    sizes it for prompt + max_new_tokens).
+    With a sampler (SamplerState) the captured step ends with the sampling kernel on its logits and
+    reads its token from the sampler's next_ids, which that kernel wrote one replay earlier:
+    advance() replays with no host-to-device token copy. Without one the graph is what it was."""
 
-    def __init__(self, model, cache: KVCache):
+    def __init__(self, model, cache: KVCache, sampler: SamplerState | None = None):
         lm = model.language_model
         self.cache, self.lm = cache, lm
         B = cache.B
         dev = cache.k.device
-        self.ids = torch.zeros(B, dtype=torch.long, device=dev)
+        self.sampler = sampler
+        self.ids = sampler.next_ids if sampler is not None else torch.zeros(B, dtype=torch.long, device=dev)
         self.pos = cache.next_pos.to(torch.int64).clone()
         self.start = torch.full((B,), cache.length, dtype=torch.int32, device=dev)
         self.embed = model.get_input_embeddings()
@@ -276,13 +354,28 @@ class DecodeGraph:
             h = layer_infer(layer, h, sctx, cache, li, 1, self.start, kv_len, attn_len=cache.max_len)
         x, _ = ops.rmsnorm_fwd(h, lm.model.norm.weight, cfg.rms_norm_eps)
         logits = ops.linear(x, lm.lm_head.weight)
+        if self.sampler is not None:  # the next step's token, written where this graph's embedding reads it
+            self.sampler.sample(logits)
         self.pos.add_(1)
         self.start.add_(1)
         return logits.view(B, 1, -1)
 
+    def advance(self):
+        """One replay of a graph with a sampler: the token the sampler holds is appended to the cache
+        and the kernel at the graph's end samples the next one (no host-to-device copy, no host read)."""
+        if self.sampler is None:
+            raise ValueError("decode graph: advance() needs a graph captured with a sampler (use step(tokens))")
+        if self.steps_left <= 0:
+            raise ValueError("decode graph: the KV cache is full")
+        self.graph.replay()
+        self.cache.length += 1
+        self.steps_left -= 1
+
     def step(self, tokens):
         """Append `tokens` ([B] ids) to the cache and return the next logits [B, 1, V] (a view of
         the graph's output buffer, overwritten by the next replay)."""
+        if self.sampler is not None:
+            raise ValueError("decode graph: a graph captured with a sampler picks its own tokens (use advance())")
         if self.steps_left <= 0:
             raise ValueError("decode graph: the KV cache is full")
         self.ids.copy_(tokens.reshape(-1))

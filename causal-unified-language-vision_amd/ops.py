@@ -23,7 +23,7 @@ __all__ = [
     "im2col_patches", "vision_embed_ln", "merge_plan", "row_gather2", "shift_targets", "ce_fwd",
     "ce_reduce", "ce_bwd", "adamw", "sumsq", "clip_coef", "scale_inplace", "kv_append", "attn_decode",
     "clip_image_preprocess", "visimage_geometry", "draw_boxes",
-    "nf4_quantize", "nf4_dequantize", "nf4_decode_linear",
+    "nf4_quantize", "nf4_dequantize", "nf4_decode_linear", "sample_token",
 ]
 
 _DT = {torch.bfloat16: DT_BF16, torch.float32: DT_F32}
@@ -654,6 +654,41 @@ def attn_bwd(q, k, v, o, do, lse, *, B: int, H: int, Lq: int, Lk: int, D: int, s
          _ptr(lse), _ptr(delta), _ptr(dq), _ld(dq), _ptr(dk), _ld(dk), _ptr(dv), _ld(dv), B, H, Lq, Lk, D,
          float(scale), int(causal), _ptr(kv_start), _dt(q), _ptr(ws), nbytes, _stream())
     return dq, dk, dv
+
+
+# ---- token sampling (csrc/sample.hip) ----------------------------------------------------------
+def sample_token(logits, *, next_ids, step, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
+                 do_sample: bool = True, seed: int = 0, row_offset=None, eos_id: int | None = None, pad_id: int = 0,
+                 finished=None, out_tokens=None, debug: int = 0):
+    """cullavo_sample_token on logits [B, V] bf16: temperature -> top-k (ties kept) -> top-p -> a
+    Philox draw keyed by (seed, row_offset[b], step[b]), or the lowest-id arg-max when not do_sample;
+    then tok = pad_id on a finished row, finished |= tok == eos_id, next_ids[b] = tok,
+    out_tokens[b, step[b]] = tok, step[b] += 1 (all in place; next_ids / step int64 [B], finished
+    uint8 [B], row_offset int64 [B] or None = the row index, out_tokens int64 [B, n] or None).
+    debug = cap > 0: also returns (keep_ids int32 [B, cap], keep_probs f32 [B, cap], n_keep int32
+    [B]), the kept tokens in canonical order; entries past n_keep keep the fill (-1 / -1.0)."""
+    _dev(logits, next_ids, step, row_offset, finished, out_tokens)
+    B, V = logits.shape
+    for name, t_, dt in (("next_ids", next_ids, torch.int64), ("step", step, torch.int64),
+                         ("row_offset", row_offset, torch.int64), ("finished", finished, torch.uint8),
+                         ("out_tokens", out_tokens, torch.int64)):
+        if t_ is None:
+            continue
+        if t_.dtype != dt or t_.shape[0] != B or (t_.dim() != (2 if name == "out_tokens" else 1)) or t_.stride(-1) != 1:
+            raise ValueError(f"sample_token: {name} must be {dt} with {B} rows and unit stride, got "
+                             f"{t_.dtype} {tuple(t_.shape)}")
+    keep = None
+    if debug:
+        keep = (torch.full((B, debug), -1, dtype=torch.int32, device=logits.device),
+                torch.full((B, debug), -1.0, dtype=torch.float32, device=logits.device),
+                torch.full((B,), -1, dtype=torch.int32, device=logits.device))
+    call("sample_token", _ptr(logits), _ld(logits), B, V, _dt(logits), float(temperature), int(top_k), float(top_p),
+         int(bool(do_sample)), int(seed) & (2 ** 64 - 1), _ptr(row_offset), _ptr(step),
+         -1 if eos_id is None else int(eos_id), int(pad_id), _ptr(finished), _ptr(next_ids), _ptr(out_tokens),
+         out_tokens.stride(0) if out_tokens is not None else 0, out_tokens.shape[1] if out_tokens is not None else 0,
+         _ptr(keep[0]) if keep else None, _ptr(keep[1]) if keep else None, _ptr(keep[2]) if keep else None,
+         int(debug), _stream())
+    return keep
 
 
 # ---- embeddings / merge ----------------------------------------------------------------------

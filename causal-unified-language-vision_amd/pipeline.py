@@ -73,12 +73,13 @@ class CuLLaVO(nn.Module):
             raise ValueError("step-2-pre generation needs a CuLLaVOProcessor (tokenizer)")
         return self.cullavo_model.step2_preprocess(batched_inputs, self.cullavo_processor, self._device(accel), **kw)
 
-    def evaluate_with_llm(self, batched_inputs, accel=None, **generate_kwargs):
+    def evaluate_with_llm(self, batched_inputs, accel=None, seed=None, **generate_kwargs):
         """reference cullavo_model.py:85-149: resize the records' images to 336x336, ask for the
         objects and their boxes, generate with the reference's sampling settings and return the
         decoded answers (the reference's version is a debugging scratchpad that overwrites its
         inputs seven times and draws with detectron2; its effective generation is this one,
-        per record, with the parsed boxes attached)."""
+        per record, with the parsed boxes attached). seed (default None: torch's global generator,
+        as before) samples on the device with generate(seed=...), record n from Philox stream n."""
         import torch.nn.functional as F
 
         from .prompting import STEP2_PRE_GENERATE, box_and_class_parser
@@ -88,7 +89,9 @@ class CuLLaVO(nn.Module):
         dev = self._device(accel)
         gk = dict(STEP2_PRE_GENERATE, **generate_kwargs)
         out = []
-        for x in batched_inputs:
+        for n, x in enumerate(batched_inputs):
+            if seed is not None:
+                gk.update(seed=seed, sample_offsets=torch.tensor([n]))
             img = F.interpolate(torch.as_tensor(x["image"])[None].float(), size=(size, size))[0]
             inputs = self.cullavo_model.eval_process(
                 images=img.round().clamp(0, 255).to(torch.uint8),

@@ -314,7 +314,7 @@ def box_and_class_parser(decoded_text: str):
 
 
 def step2_preprocess(model, batched_inputs, processor, device, *, dice=None, generate_kwargs=None, on_generate=None,
-                     vis_dir=None):
+                     vis_dir=None, seed=None):
     """reference cullavo/arch_cullavo.py:341-395: for one record in ~50 (torch.randint(0, 50) == 0)
     generate an object/box description of its image with the reference's sampling settings
     (T 0.9, top-k 50, top-p 0.95, 1000 new tokens, KV cache), parse boxes and classes, and emit
@@ -323,8 +323,12 @@ def step2_preprocess(model, batched_inputs, processor, device, *, dice=None, gen
     debugging render (:376-386, visualize.render_boxes_and_labels); a failing render emits the
     record without boxes, as the reference's bare except does. dice(record) replaces
     the random roll, generate_kwargs override the sampling settings (tests: greedy),
-    on_generate(record, generate_ids, decoded_text) observes each generation."""
+    on_generate(record, generate_ids, decoded_text) observes each generation. seed (default None:
+    torch's global generator, as before) samples on the device with generate(seed=...): the n-th
+    generation of the call draws from Philox stream n, so a record's text does not depend on how
+    the records are batched or on what was generated before it."""
     gk = dict(STEP2_PRE_GENERATE, **(generate_kwargs or {}))
+    n_generated = 0
     new = []
     for batch in batched_inputs:
         if "image" not in batch:
@@ -337,6 +341,9 @@ def step2_preprocess(model, batched_inputs, processor, device, *, dice=None, gen
             continue
         inputs = eval_process(images=batch["image"], prompt=STEP2_PRE_PROMPT, processor=processor, device=device,
                               ignore_index=model.config.ignore_index)
+        if seed is not None:
+            gk.update(seed=seed, sample_offsets=torch.tensor([n_generated]))
+        n_generated += 1
         with torch.inference_mode():
             ids = model.generate(**inputs, **gk)
         text = processor.batch_decode(ids, skip_special_tokens=True)[0]

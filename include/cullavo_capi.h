@@ -56,7 +56,9 @@ extern "C" {
    attention and GEMV variants removed with them: the attention backward's staging setter, the
    decode GEMV's non-temporal-load setter, and the retired values of cullavo_attn_set_stage /
    cullavo_attn_set_bwd_tiles; 7: the supervised-row entry points cullavo_rmsnorm_fwd_rows,
-   cullavo_rmsnorm_bwd_rows and cullavo_rows_scatter added; 8: cullavo_attn_fwd_cached added). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
+   cullavo_rmsnorm_bwd_rows and cullavo_rows_scatter added; 8: cullavo_attn_fwd_cached added). cullavo_sample_token
+   was added under 8 without a bump, as cullavo_lora_dx was under its version: a pure addition that
+   changes no existing signature. A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
 #define CULLAVO_ABI_VERSION 8
 
 int cullavo_abi_version(void);
@@ -447,6 +449,38 @@ size_t cullavo_attn_decode_workspace(int B, int H, int max_len, int D);
 int cullavo_attn_decode(const void* q, int64_t ldq, const void* k_cache, const void* v_cache, int64_t ld_tok,
                         int64_t ld_batch, const int32_t* kv_len, const int32_t* kv_start, void* o, int64_t ldo,
                         int B, int H, int max_len, int D, float scale, float* workspace, void* stream);
+
+/* ---- token sampling (generate; added under ABI 8) ---------------------------------------------
+ * Replaces HF's logits warpers and multinomial behind the reference's
+ * generate(do_sample=True, temperature=0.9, top_k=50, top_p=0.95, max_new_tokens=1000)
+ * (cullavo/arch_cullavo.py:362-365), in HF's warper order temperature -> top-k -> top-p -> draw,
+ * plus generate()'s eos / pad bookkeeping: one launch, one workgroup per row, captured at the end
+ * of the decode graph so that the next step's input token never leaves the device.
+ *   logits [B, V] bf16 (ldl >= V); temperature > 0 and finite; 1 <= top_k <= 1024; 0 < top_p <= 1;
+ *   do_sample 0 = greedy (the lowest-id arg-max; the warper parameters are still validated).
+ *   x = f32(logit) / temperature (a true division). Top-k keeps every token with x >= the k-th
+ *   largest x: ties with the k-th value all survive (masked_fill(x < kth)); V < top_k keeps all.
+ *   Canonical order: descending x, equal values by ascending token id. Top-p: with p = the f32
+ *   softmax over the survivors, a survivor is removed iff the mass of itself plus everything after
+ *   it in canonical order is <= 1 - top_p (within a tie run the highest ids go first); the first
+ *   token always stays; top_p = 1 removes nothing. Draw: the first token in canonical order whose
+ *   running sum exceeds u * (kept mass), u = (word0 >> 8) * 2^-24 of Philox4x32-10 (Random123
+ *   constants) with key = (seed low, seed high) and counter = (step[b] low, step[b] high,
+ *   row_offset[b] low, row_offset[b] high); row_offset NULL = the row index.
+ *   tok = finished[b] ? pad_id : drawn; finished[b] |= tok == eos_id (eos_id -1: none; finished
+ *   NULL: no row is finished); next_ids[b] = tok; out_tokens[b, step[b]] = tok when
+ *   step[b] < n_out (out_tokens nullable, ld_out >= n_out); then step[b] += 1.
+ *   Debug outputs (NULL in production): n_keep [B] the number of kept tokens; keep_ids /
+ *   keep_probs [B, cap] the first min(n_keep, cap) kept tokens in canonical order with the
+ *   probabilities the draw uses (renormalised over the kept set); entries past that are not written.
+ * Deterministic: integer histograms, float sums by scans in a fixed order; a row's result does
+ * not depend on the rows launched with it. top_k = 0 (nucleus over the full vocabulary),
+ * repetition penalties and beam search are not implemented. */
+int cullavo_sample_token(const void* logits, int64_t ldl, int B, int64_t V, int dtype, float temperature,
+                         int top_k, float top_p, int do_sample, uint64_t seed, const int64_t* row_offset,
+                         int64_t* step, int64_t eos_id, int64_t pad_id, uint8_t* finished,
+                         int64_t* next_ids, int64_t* out_tokens, int64_t ld_out, int64_t n_out,
+                         int32_t* keep_ids, float* keep_probs, int32_t* n_keep, int64_t cap, void* stream);
 
 /* ---- image preprocessing (data step) --------------------------------
  * Replaces the CLIPImageProcessor call inside the reference's prompt builders
