@@ -131,7 +131,12 @@ __global__ __launch_bounds__(256) void attn_decode_k(const u16* __restrict__ Q, 
 #pragma unroll
     for (int i = 0; i < kChunk / 16; ++i) {
       const int k = min(kg + 16 * i, nk - 1);
-      vr[i] = *reinterpret_cast<const u16x8*>(Vb + (int64_t)(kbeg + k) * ld_tok + dg * 8);
+      // a key below kv_start has p = 0 and its V row is not read: a free cache row there may hold
+      // anything, NaN included (the contract of attn_fwd_cached), and 0 * NaN must not reach the sum.
+      // For a finite row this puts 0 * 0 = +0 in place of 0 * v on an accumulator that starts at +0:
+      // the same bits.
+      vr[i] = u16x8{};
+      if (kbeg + k >= k_lo) vr[i] = *reinterpret_cast<const u16x8*>(Vb + (int64_t)(kbeg + k) * ld_tok + dg * 8);
     }
     __syncthreads();
     if (has_new) {  // the appended row from LDS (this workgroup's own cache write may not be visible)

@@ -76,6 +76,11 @@ def test_attn_decode_matches_softmax():
         ref = (p[:, None, :] @ vh).squeeze(1).reshape(-1)
         err = (o[b].float().cpu() - ref).abs().max().item()
         assert err <= 1e-2 * ref.abs().max().item(), (b, err)
+    # per element against f64 (tests/decode_refs.py: one bf16 rounding + the f32 summation bound)
+    from tests import decode_refs as R
+    ref64, pv_abs, n = R.decode_attn_ref(q.cuda(), kc.cuda(), vc.cuda(), kv_start.cuda(), kv_len.cuda(), D ** -0.5)
+    worst, zero_ok = R.attn_gate(o, ref64, pv_abs, n)
+    assert worst <= 1.0 and zero_ok, worst
 
 
 # ---------------------------------------------------------------------------------------------

@@ -554,8 +554,16 @@ def test_rope(D, H):
     ops().rope(qd, kd, pos.to(DEV), hq=H, hk=H, head_dim=D, theta=10000.0)
     close(qd, ref(q), 8e-3, "rope q")
     close(kd, ref(k), 8e-3, "rope k")
+    # per element against the exact f64 rotation (tests/decode_refs.py: 4 U (|x1| + |x2|) per pair)
+    from tests import decode_refs as R
+    for out, x in ((qd, q), (kd, k)):
+        w = R.rope_gate(out, x.to(DEV), pos.to(DEV), D)
+        assert w <= 1.0, f"rope err / gate {w:.3f}"
     ops().rope(qd, kd, pos.to(DEV), hq=H, hk=H, head_dim=D, theta=10000.0, inverse=True)
     close(qd, q.float(), 2e-2, "rope inverse")
+    for out, x in ((qd, q), (kd, k)):
+        w = R.worst(out.double() - x.to(DEV).double(), 8 * R.U * R.rope_pair_abs(x.to(DEV), D))
+        assert w <= 1.0, f"rope inverse(forward) err / gate {w:.3f}"
 
 
 # ---------------------------------------------------------------------------------------------
