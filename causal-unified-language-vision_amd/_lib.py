@@ -81,6 +81,16 @@ def abi_version(path: str = HEADER) -> int:
     return int(re.search(r"#define CULLAVO_ABI_VERSION (\d+)", open(path).read()).group(1))
 
 
+def _switch01(var: str) -> int:
+    """A GEMM switch from the environment: 0 or 1. bench.py reads the same variables to predict kernel
+    names, so a value the library would ignore must not pass silently."""
+    v = os.environ[var].strip()
+    if v not in ("0", "1"):
+        raise RuntimeError(f"{var}={v!r}: only 0 or 1 since ABI 9 (the other values' kernels and plans were "
+                           "measured and removed, see DESIGN.md)")
+    return int(v)
+
+
 def lib():
     """Load and bind the HIP library (raises if it is absent: there is no CPU fallback)."""
     global _lib
@@ -99,26 +109,22 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = [_argtype(t) for t, _ in params]
             fn.restype = {"int": ctypes.c_int, "size_t": ctypes.c_size_t}.get(ret, ctypes.c_char_p)
-        _lib = L
         # tuning switches for A/B runs (tools, bench): kernel-choice overrides from the env
         if os.environ.get("CULLAVO_ATTN_BWD_MODE"):
             L.cullavo_attn_set_bwd_tiles(int(os.environ["CULLAVO_ATTN_BWD_MODE"]))
         if os.environ.get("CULLAVO_GEMM_TILE"):
             L.cullavo_gemm_set_tile(int(os.environ["CULLAVO_GEMM_TILE"]))
-        if os.environ.get("CULLAVO_SPLITK_TARGET"):  # split-K plan A/B (cullavo_gemm_set_splitk_target)
-            L.cullavo_gemm_set_splitk_target(int(os.environ["CULLAVO_SPLITK_TARGET"]))
-        if os.environ.get("CULLAVO_GEMM_MSPLIT"):  # M-tail split A/B (cullavo_gemm_set_msplit)
-            L.cullavo_gemm_set_msplit(int(os.environ["CULLAVO_GEMM_MSPLIT"]))
+        if os.environ.get("CULLAVO_GEMM_MSPLIT"):  # M-tail / round split A/B (cullavo_gemm_set_msplit)
+            L.cullavo_gemm_set_msplit(_switch01("CULLAVO_GEMM_MSPLIT"))
         if os.environ.get("CULLAVO_GEMM_GROUP"):  # tile-order A/B (cullavo_gemm_set_group)
             L.cullavo_gemm_set_group(int(os.environ["CULLAVO_GEMM_GROUP"]))
-        if os.environ.get("CULLAVO_GEMM_EPILOGUE"):  # epilogue A/B: bit 0 LDS-staged, bit 1 nt stores
-            L.cullavo_gemm_set_epilogue(int(os.environ["CULLAVO_GEMM_EPILOGUE"]))
+        if os.environ.get("CULLAVO_GEMM_EPILOGUE"):  # epilogue A/B: 1 the 16-B epilogues, 0 per-lane stores
+            L.cullavo_gemm_set_epilogue(_switch01("CULLAVO_GEMM_EPILOGUE"))
         if os.environ.get("CULLAVO_GEMM_DMA"):  # DMA-offset A/B (cullavo_gemm_set_dma)
             L.cullavo_gemm_set_dma(int(os.environ["CULLAVO_GEMM_DMA"]))
-        if os.environ.get("CULLAVO_RATE288") is not None:  # 288-row tile A/B (0 = out of the plan)
-            L.cullavo_gemm_set_tile_rate(10, float(os.environ["CULLAVO_RATE288"]), None)
         if os.environ.get("CULLAVO_ATTN_RESCALE"):  # deferred-rescale A/B (cullavo_attn_set_rescale)
             L.cullavo_attn_set_rescale(float(os.environ["CULLAVO_ATTN_RESCALE"]), None)
+        _lib = L  # bound only once every switch was accepted: a refused value raises on every call
     return _lib
 
 

@@ -123,11 +123,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_k(GemmArgs p, int splits) {
   }
 }
 
-// LDR selects which waves stage the next K-tile: 0 = all eight (each wave issues its share of
-// LDS-DMA pieces before its MFMAs, so both waves of a SIMD stall on DMA issue together);
-// 1 = waves 0-3 only, 2 = waves 4-7 only (one loader per SIMD: its DMA issue runs beside the
-// partner wave's MFMAs instead of beside nothing). Data-parallel blocks: one whole tile each,
-// the sk_dp tiles of the grid.
 // Fused LoRA up-projection (round 4; the reference recipe's peft adapters, cullavo/load_cullavo.py:
 // 94-112): after the main K loop each lane rounds its base outputs v = round(alpha*acc + bias) into
 // packed bf16 registers, the tile's u rows (this N-tile's module block, 64 wide) and lora_B rows
@@ -196,7 +191,7 @@ DEV void lora_fuse(GemmArgs& p, f32x4 (&acc)[TMW][TN], char* smem, int staged, i
 }
 
 // EPI > 0: the direct epilogue (direct_epilogue, lean case EPI - 1) instead of the LDS-staged one,
-// chosen by the host per product (launch256_lean)
+// chosen by the host per product (launch256_lean). LDR is always 1 (tile_k_range)
 template <int AL, int BL, int CT, int BMT, int BN, int LDR = 0, bool LORA = false, bool SWG = false, int EPI = 0>
 __global__ __launch_bounds__(512, 1) void gemm256_k(GemmArgs p) {
   constexpr int BM2 = BMT;  // 256 or 192 (192 only with a K-contiguous A)
@@ -266,16 +261,8 @@ __global__ __launch_bounds__(512, 1) void gemm256_k(GemmArgs p) {
 }
 
 
-
 int num_cus();
-// ---- persistent 256x256 forward kernel (round 5) ---------------------------------------------
-// Layout (0,0), bf16 C, no split-K / LoRA: one 512-thread block per CU walks the tiles of the grid in
-// the data-parallel kernel's lock-step round order (tile t, t + gridDim, ...; the same XCD remap and
-// group order), the same LDS-DMA K-loop (waves 0-3 load), the next tile's first K-tile issued under
-// the current tile's last MFMAs, and the LDS epilogue in four 64-row passes through the stage the
-// last K-tile freed (64 KiB), each 8-column group written by lds_store_item (the lean paths of
-// lds_epilogue and store8 otherwise: the same values as gemm256_k). Lab record:
-// tools/lab/gemm256p_lab.hip, profiles/r05/gemm/persistent_lab.txt and epilogue/.
+
 struct PTile { int tm, tn; };
 DEV PTile ptile(const GemmArgs& p, int lid) {  // tile_origin's order by value selects
   const bool by_n = p.group_m < 0;
@@ -298,114 +285,11 @@ DEV void praw_barrier() {
   __builtin_amdgcn_sched_barrier(0);
 }
 
-constexpr int P_TA = 256 * BK * 2, P_STAGE = 2 * P_TA;  // 32 KiB A + 32 KiB B per stage
-
-template <int Q, int MODE>
-DEV void p_epi_pass(const GemmArgs& p, f32x4 (&acc)[8][4], char* ep, int64_t m0, int64_t n0, int wm, int wn, int el) {
-  const int elane = el & 63;
-  if (wm == (Q >> 1)) {
-#pragma unroll
-    for (int t4 = 0; t4 < 4; ++t4)
-#pragma unroll
-      for (int tn = 0; tn < 4; ++tn) {
-        const int r = t4 * 16 + (elane & 15);
-        const int c = wn * 16 + tn * 4 + (elane >> 4);
-        *reinterpret_cast<f32x4*>(ep + r * 1024 + ((c ^ (r & 15)) << 4)) = acc[(Q & 1) * 4 + t4][tn];
-      }
-  }
-  praw_barrier();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int idx = el + 512 * i;
-    const int r = idx >> 5, pr = idx & 31;
-    const int sw = (pr >> 3) & 1;
-    const int c0 = 2 * pr + sw, c1 = 2 * pr + 1 - sw;
-    const char* rowp = ep + r * 1024;
-    const f32x4 x0 = *reinterpret_cast<const f32x4*>(rowp + ((c0 ^ (r & 15)) << 4));
-    const f32x4 x1 = *reinterpret_cast<const f32x4*>(rowp + ((c1 ^ (r & 15)) << 4));
-    const f32x4 lo = sw ? x1 : x0, hi = sw ? x0 : x1;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] = lo[j]; v[4 + j] = hi[j]; }
-    lds_store_item<CULLAVO_DT_BF16>(p, v, m0 + Q * 64 + r, n0 + pr * 8, MODE);
-  }
-  praw_barrier();
-}
-
-// MODE: lds_epi_mode's case, fixed per instantiation (a runtime mode per 8-column group kept every
-// path's code in the epilogue and measured slower than the data-parallel kernel)
-template <int MODE>
-__global__ __launch_bounds__(512, 1) void gemm256p_k(GemmArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  const bool loader = wave < 4;
-  const int lw = wave & 3;
-  const int tiles = p.tiles_m * p.tiles_n;
-  const int nk = (int)cdiv(p.K, BK);
-  int t = blockIdx.x;
-  if (t >= tiles) return;
-  const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.A, ((p.M - 1) * p.lda + p.K) * 2);
-  const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.B, ((p.N - 1) * p.ldb + p.K) * 2);
-  PTile xy = ptile(p, xcd_remap(t, p.sk_dp));
-  int64_t m0 = (int64_t)xy.tm * 256, n0 = (int64_t)xy.tn * 256;
-  if (loader) {
-    dma_tile<0, 256, 4>(ra, p.lda, m0, p.M, 0, p.K, smem, lw, lane);
-    dma_tile<0, 256, 4>(rb, p.ldb, n0, p.N, 0, p.K, smem + P_TA, lw, lane);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  praw_barrier();
-  int s = 0;
-  f32x4 acc[8][4];
-  for (;;) {
-    const int t1 = t + (int)gridDim.x;
-    const bool has_next = t1 < tiles;
-    const PTile xy1 = ptile(p, xcd_remap(has_next ? t1 : t, p.sk_dp));
-    const int64_t m1 = (int64_t)xy1.tm * 256, n1 = (int64_t)xy1.tn * 256;
-    unsigned va[dma_per<256, 4>()], vb[dma_per<256, 4>()];
-    dma_prep<0, 256, 4>(p.lda, m0, p.M, lw, lane, va);
-    dma_prep<0, 256, 4>(p.ldb, n0, p.N, lw, lane, vb);
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt < nk; ++kt) {
-      char* cur = smem + ((s + kt) & 1) * P_STAGE;
-      char* nxt = smem + ((s + kt + 1) & 1) * P_STAGE;
-      if (loader) {
-        if (kt + 1 < nk) {
-          const int64_t k1 = (int64_t)(kt + 1) * BK;
-          dma_issue<256, 4>(ra, va, dma_soff<0>(k1, p.lda), nxt, lw);
-          dma_issue<256, 4>(rb, vb, dma_soff<0>(k1, p.ldb), nxt + P_TA, lw);
-        } else if (has_next) {  // the next tile's first K-tile under this tile's last MFMAs
-          dma_tile<0, 256, 4>(ra, p.lda, m1, p.M, 0, p.K, nxt, lw, lane);
-          dma_tile<0, 256, 4>(rb, p.ldb, n1, p.N, 0, p.K, nxt + P_TA, lw, lane);
-        }
-      }
-      tile_mfma<0, 0, 256, 256, 8, 4>(cur, wm, wn, lane, acc);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      praw_barrier();
-    }
-    char* ep = smem + ((s + nk - 1) & 1) * P_STAGE;  // the last K-tile's stage, free after the barrier
-    // per-lane epilogue indices behind an opaque copy (hoisted out of the tile loop they would stay
-    // live across the K-loop and spill)
-    int el = (int)threadIdx.x;
-    asm volatile("" : "+v"(el));
-    p_epi_pass<0, MODE>(p, acc, ep, m0, n0, wm, wn, el);
-    p_epi_pass<1, MODE>(p, acc, ep, m0, n0, wm, wn, el);
-    p_epi_pass<2, MODE>(p, acc, ep, m0, n0, wm, wn, el);
-    p_epi_pass<3, MODE>(p, acc, ep, m0, n0, wm, wn, el);
-    if (!has_next) break;
-    s = (s + nk) & 1;
-    t = t1;
-    m0 = m1;
-    n0 = n1;
-  }
-}
-
-// ---- persistent forward kernel with the direct epilogue (round 6) ------------------------------
-// gemm256p_k's tile walk and K-loop, with (a) the epilogue written straight from the accumulators by
+// ---- persistent forward kernel with the direct epilogue (rounds 5 and 6) ------------------------
+// Layout (0,0), bf16 C, no split-K / LoRA: one 512-thread block per CU walks the tiles of the grid in
+// the data-parallel kernel's lock-step round order (tile t, t + gridDim, ...; the same XCD remap and
+// group order, ptile), with the same LDS-DMA K-loop (waves 0-3 load) and the next tile's first K-tile
+// issued under the current tile's last MFMAs; (a) the epilogue written straight from the accumulators by
 // direct_epilogue (permlane16-widened 16-B buffer stores, no LDS round trip, no barrier), (b) the next
 // tile's K-tile 1 issued by the loader waves BEFORE those stores (into the stage this tile's last
 // K-tile freed), so the stores drain under the next tile's K-tile 0 (the loaders' first wait is a
@@ -413,7 +297,9 @@ __global__ __launch_bounds__(512, 1) void gemm256p_k(GemmArgs p) {
 // offsets as one lane base + a scalar row stride behind an opaque copy (rows past M land past the
 // buffer's num_records), which keeps 16 offset registers out of the K-loop. Lab:
 // tools/lab/gemm_hc_lab.hip variant 2 (profiles/r06/gemm/hc_lab.txt): ViT K = 1024 products +5-9 %,
-// gate|up / lm_head +2-3 % over gemm256p_k.
+// gate|up / lm_head +2-3 % over round 5's gemm256p_k, the same walk with an LDS-staged epilogue in
+// four 64-row passes (measured and removed in ABI 9; tools/lab/gemm256p_lab.hip,
+// profiles/r05/gemm/persistent_lab.txt).
 DEV unsigned dma_base0(int64_t ld, int64_t idx0, int lw, int lane) {
   const int row = lw * 8 + (lane >> 3);
   const int chunk = (lane & 7) ^ ((row >> 1) & 7);  // the same for every piece (+32 rows)
@@ -521,24 +407,6 @@ __global__ __launch_bounds__(512, 1) void gemm256pd_k(GemmArgs p) {
   }
 }
 
-int g_persist = 1;  // cullavo_gemm_set_epilogue bit 5 turns the persistent forward kernel off (A/B)
-
-template <int MODE>
-int launch256p_m(GemmArgs p, hipStream_t s) {
-  const int smem = 2 * P_STAGE;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm256p_k<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  p.tiles_m = (int)cdiv(p.M, 256);
-  p.tiles_n = (int)cdiv(p.N, 256);
-  p.sk_dp = p.tiles_m * p.tiles_n;
-  const int grid = std::min(p.sk_dp, num_cus());
-  gemm256p_k<MODE><<<(unsigned)grid, 512, smem, s>>>(p);
-  return cullavo_check_launch("gemm256 persistent");
-}
-
 template <int MODE, int BMT = 256>
 int launch256pd_m(GemmArgs p, hipStream_t s) {
   const int smem = 2 * (BMT * BK * 2 + 256 * BK * 2);
@@ -556,36 +424,21 @@ int launch256pd_m(GemmArgs p, hipStream_t s) {
   return cullavo_check_launch("gemm256 persistent direct");
 }
 
-// the lean epilogue case of a product (lds_epi_mode's 0 plain, 1 bias / residual, 2 activation), or
-// -1 (the general path); on the host, the same conditions
-int lean_mode(const GemmArgs& p) {
-  const bool lean = p.act == CULLAVO_ACT_NONE && p.preact == nullptr && p.addend == nullptr && p.beta == 0.f &&
-                    p.drop_mode != 3 && !p.nt_store;
-  if (lean && p.bias == nullptr && p.residual == nullptr && !(p.epi_lds & 8)) return 0;
-  if (lean && !(p.epi_lds & 4) && !(p.bias == nullptr && p.residual == nullptr)) return 1;
-  if (p.act != CULLAVO_ACT_NONE && p.act != CULLAVO_ACT_SWIGLU_BWD && p.preact == nullptr && p.addend == nullptr &&
-      p.residual == nullptr && p.beta == 0.f && p.drop_mode != 3 && !p.nt_store && !(p.epi_lds & 16))
-    return 2;
-  return -1;
-}
-
 // C (the direct epilogue's stores) and the residual (its loads) addressable by one buffer descriptor each
 bool c_fits_rsrc(const GemmArgs& p) {
   return ((p.M - 1) * p.ldc + p.N) * 2 < (int64_t)kOOB &&
          (p.residual == nullptr || ((p.M - 1) * p.ldr + p.N) * 2 < (int64_t)kOOB);
 }
 
-// the persistent 288-row direct kernel for a lean (0,0) product; -1: not eligible. Always at K < 2048
-// or N <= 2048 (the ViT's products: K = 1024 on 288-row tiles since round 6, fc2 N = 1024): fc1 / o
-// 920 / 825 -> 940 / 880 TF/s with the plan's 288-row M-split; ViT step 2481 (round 5's plan) ->
-// 2488 (288 rows at short K) -> 2496 img/s (and fc2 persistent), alternating on one box
-// (profiles/r06/gemm/vit288_ab.txt). Otherwise opt-in (cullavo_gemm_set_epilogue bit 8): on one box
-// (tools/epi_ab.py, profiles/r06/gemm/epi_ab.txt) it beat the data-parallel 288-row direct kernel on
-// gate|up (1349 vs 1340 TF/s) but lost on q|k|v, o and down (1358 / 1284 / 1305 vs 1390 / 1317 / 1314)
+// the persistent 288-row direct kernel for a lean (0,0) product; -1: not eligible. At K < 2048 or
+// N <= 2048 (the ViT's products: K = 1024 on 288-row tiles since round 6, fc2 N = 1024): fc1 / o
+// 920 / 825 -> 940 / 880 TF/s with the plan's 288-row M-split, ViT step 2481 -> 2496 img/s
+// (profiles/r06/gemm/vit288_ab.txt). At K >= 2048 and N > 2048 it lost to the data-parallel 288-row
+// direct kernel on three of four shapes (measured and removed in ABI 9, profiles/r06/gemm/epi_ab.txt)
 int launch288pd(const GemmArgs& p, hipStream_t s) {
-  if (!(p.epi_lds & 256) && p.K >= 2048 && p.N > 2048) return -1;
-  if (p.part != nullptr || !p.epi_lds || (p.epi_lds & (128 | 32)) || !p.dma_pre || !c_fits_rsrc(p)) return -1;
-  const int mode = lean_mode(p);
+  if (p.K >= 2048 && p.N > 2048) return -1;
+  if (p.part != nullptr || !p.epi_lds || !p.dma_pre || !c_fits_rsrc(p)) return -1;
+  const int mode = lean_case(p);
   if (mode == 0) return launch256pd_m<0, 288>(p, s);
   if (mode == 1) return launch256pd_m<1, 288>(p, s);
   if (mode == 2) return launch256pd_m<2, 288>(p, s);
@@ -593,24 +446,21 @@ int launch288pd(const GemmArgs& p, hipStream_t s) {
 }
 
 // the persistent kernel for the lean epilogue cases (plain, bias / residual, activation); -1: none.
-// cullavo_gemm_set_epilogue bit 7 keeps the LDS-staged epilogue (gemm256p_k) for A/B
+// A C or residual of 2 GiB or more (one buffer descriptor cannot address it) used to run the LDS-staged
+// persistent kernel; since ABI 9 it falls through to the data-parallel LDS-staged kernel (same bits)
 int launch256p(const GemmArgs& p, hipStream_t s) {
-  const int mode = lean_mode(p);
-  if (mode < 0) return -1;
-  if (!(p.epi_lds & 128) && c_fits_rsrc(p)) {
-    if (mode == 0) return launch256pd_m<0>(p, s);
-    if (mode == 1) return launch256pd_m<1>(p, s);
-    return launch256pd_m<2>(p, s);
-  }
-  if (mode == 0) return launch256p_m<0>(p, s);
-  if (mode == 1) return launch256p_m<1>(p, s);
-  return launch256p_m<2>(p, s);
+  const int mode = lean_case(p);
+  if (mode < 0 || !c_fits_rsrc(p)) return -1;
+  if (mode == 0) return launch256pd_m<0>(p, s);
+  if (mode == 1) return launch256pd_m<1>(p, s);
+  return launch256pd_m<2>(p, s);
 }
 
 // Split-K plan for the register-staged kernel: products whose 128x128 tile grid cannot fill
 // the 256 CUs but whose K is long (the LoRA adapter GEMMs: N or M = r = 64, K = tokens or
-// features) are cut into K chunks of >= 4 K-tiles, enough of them for ~512 workgroups.
-int g_splitk_blocks = 512;  // target blocks of a split-K launch (cullavo_gemm_set_splitk_target)
+// features) are cut into K chunks of >= 4 K-tiles, enough of them for ~512 workgroups (a sweep of
+// that target kept 512: measured, its switch removed in ABI 9, profiles/r06/gemm/splitk_target_vit_ab.txt).
+constexpr int g_splitk_blocks = 512;
 
 // Split-K plan for the 8-wave 256x256 kernel: products whose 256x256 grid fills at most a
 // quarter of the CUs while K is long (the ViT's fc2 at 4 images: 2308 x 1024 x 4096; the
@@ -621,7 +471,6 @@ int g_splitk_blocks = 512;  // target blocks of a split-K launch (cullavo_gemm_s
 // costs more than the idle CUs (2308 x 3072 x 1024: 223 split vs 514 TF/s unsplit), at K >= 4096
 // the split wins (4096 x 1024 x 4608 dW: 652 vs 492). Both M and N >= 256 (else the 256-wide
 // tile is mostly padding: the register-staged 128x128 split below takes those).
-int num_cus();
 
 // Split over K when the 256x256 grid covers at most half the CUs and K is long (>= 32 K-tiles):
 // e.g. the ViT's fc2 at 8 images (4616 x 1024 x 4096: 76 tiles -> 3 splits, 228 blocks).
@@ -710,8 +559,8 @@ int launch256(GemmArgs p, hipStream_t s) {
 // when the product is not one of them (the LDS-staged general epilogue then runs)
 template <int AL, int BL, int BM2>
 int launch256_lean(const GemmArgs& p, hipStream_t s) {
-  if (p.part != nullptr || !p.epi_lds || (p.epi_lds & 128) || !c_fits_rsrc(p)) return -1;
-  const int mode = lean_mode(p);
+  if (p.part != nullptr || !p.epi_lds || !c_fits_rsrc(p)) return -1;
+  const int mode = lean_case(p);
   if (mode == 0) return launch256<AL, BL, CULLAVO_DT_BF16, BM2, 256, false, false, 1>(p, s);
   if (mode == 1) return launch256<AL, BL, CULLAVO_DT_BF16, BM2, 256, false, false, 2>(p, s);
   return -1;
@@ -734,26 +583,24 @@ int launch256_lean(const GemmArgs& p, hipStream_t s) {
 // over the 4 loader waves). The per-K-tile overhead (barrier, DMA issue, fragment-read latency)
 // is roughly fixed, so a taller tile amortises it over more MFMAs, and M = 8704 = 30.2 x 288
 // makes the N = 4096 products (every dX, o and down forward) 496 tiles = 1.94 rounds instead of
-// 736 192-row tiles = 2.88 rounds.
+// 736 192-row tiles = 2.88 rounds. At every K since round 6 (the direct epilogue and the persistent
+// 288-row kernel, launch288pd); round 3's K >= 2048 rule was measured and removed in ABI 9
+// (profiles/r06/gemm/vit288_ab.txt).
 // Round 5 tried a 4-wave 256x256 kernel (one wave per SIMD, AGPR accumulators, register- or
 // LDS-DMA-staged, with and without a stream-K head): equal or slower on every step shape, kept
 // in tools/lab/gemm4w_r5.hip with its ablations (profiles/r05/gemm/).
 enum { kT128 = 0, kT256x256 = 2, kT192x256 = 3, kT288x256 = 10 };
-// plan rates of tile modes 2, 3, 10 (cullavo_gemm_set_tile_rate)
-double g_tile_rate[3] = {1300.0, 1150.0, 1360.0};
+// plan rates of tile modes 2, 3, 10 (a sweep of the 288-row rate kept it: measured, the rate switch
+// removed in ABI 9, profiles/r06/gemm/rate288_ab.txt)
+constexpr double g_tile_rate[3] = {1300.0, 1150.0, 1360.0};
 // M-tail split (round 5): when M is just past a multiple of a tile's height, its last M-tile row
 // is mostly padding and can cost a whole extra round (the ViT's M = 64 x 577 = 36928 = 144 x 256
 // + 64: fc1 at 256x256 is 2,320 tiles = 9.06 rounds -> 10; fc2 / o at 288x256 are 516 tiles =
 // 2.02 rounds -> 3). The plan then runs rows [0, m_main) (m_main = a multiple of the tile height)
 // on that tile and the remaining rows as a second, thin product (128x128 tiles, split over K
-// when the caller gives the workspace), if that is estimated faster: g_msplit 2 (the default since
-// round 6) on any estimated gain, 1 only on >= 5 % (round 5's rule, which left fc1 unsplit: its
-// estimate is 3 %; split, fc1 runs 902 -> 928 TF/s and the ViT step 2505 -> 2518 img/s,
-// profiles/r06/gemm/msplit_eager_ab.txt).
-int g_msplit = 2;
-// 288-row tiles at K < 2048 (round 6, with the persistent 288-row direct kernel: launch288pd);
-// cullavo_gemm_set_epilogue bit 9 restores the round-3 exclusion below
-int g_short288 = 1;
+// when the caller gives the workspace), on any estimated gain. (Round 5's rule, only on >= 5 %, left
+// fc1 unsplit: measured and removed in ABI 9, profiles/r06/gemm/msplit_eager_ab.txt.)
+bool g_msplit = true;  // cullavo_gemm_set_msplit
 // the thin product's time: its split-K launch + reduce cost 16-19 us at the ViT shapes (64 rows:
 // profiles/r05/vit/vit_kernel_trace.txt), so a split pays only where it saves more than that --
 // fc2 (K = 4096: 3 -> 2 rounds of 288-row tiles), not fc1 / o (K = 1024)
@@ -790,12 +637,6 @@ int choose_tile(int64_t M, int64_t N, int64_t K, int a_layout, int force, int64_
   int64_t mm_split = 0;
   for (const C& c : cands) {
     if ((c.id == kT192x256 || c.id == kT288x256) && a_layout != 0) continue;
-    // round 3: 288 rows only for long K -- with 16 K-tiles (the ViT's K = 1024 products) its larger
-    // per-tile prologue and 144 KiB LDS-staged epilogue cost more than the rounds it saved (config 2:
-    // fc1 36928x4096x1024 at 815 TF/s against 865 for the 256-row tile); with the direct epilogue
-    // and the persistent 288-row kernel (round 6) short K takes it too, unless bit 9
-    if (c.id == kT288x256 && K < 2048 && !g_short288) continue;
-    if (c.rate <= 0.0) continue;
     const double t = seconds(c, M);
     if (t < best * 0.999) { best = t; bid = c.id; }
     const int64_t mm = M / c.bm * c.bm;
@@ -821,7 +662,7 @@ int choose_tile(int64_t M, int64_t N, int64_t K, int a_layout, int force, int64_
       }
     }
   }
-  if (m_main && best_split < (g_msplit == 2 ? 0.999 : 0.95) * best) {
+  if (m_main && best_split < 0.999 * best) {
     *m_main = mm_split;
     return bid_split;
   }
@@ -835,18 +676,11 @@ static int g_gemv = 1;  // cullavo_gemm_set_tile(mode >= 0) forces a tiled kerne
 static bool gemv_eligible(int64_t M, int a_layout, int b_layout, bool dropping) {
   return g_gemv && g_force_tile < 0 && M >= 1 && M <= 16 && a_layout == 0 && b_layout == 0 && !dropping;
 }
-static int g_epi_lds = 1;
-static int g_nt_store = 0;
+static int g_epi_lds = 1;  // cullavo_gemm_set_epilogue: 1 the 16-B epilogues, 0 per-lane stores
 static int g_dma_pre = 1;  // +2.7 % on the 7B step (profiles/r03/dma_ab.md)
 // Groups of 4 N-tiles sweeping the M-tiles: measured against groups of 4 M-tiles on every 7B
 // step shape in one process (profiles/r02/closing/group_sweep.txt), 1-5 % faster on 13 of 15.
 static int g_group_m = -4;
-
-extern "C" int cullavo_gemm_set_splitk_target(int blocks) {
-  const int prev = g_splitk_blocks;
-  if (blocks >= 64 && blocks <= 8192) g_splitk_blocks = blocks;
-  return prev;
-}
 
 extern "C" int cullavo_gemm_set_group(int group) {
   const int prev = g_group_m;
@@ -860,15 +694,6 @@ extern "C" int cullavo_gemm_set_tile(int mode) {
   return prev;
 }
 
-extern "C" int cullavo_gemm_set_tile_rate(int mode, float tflops, float* previous) {
-  const int i = mode == kT256x256 ? 0 : mode == kT192x256 ? 1 : mode == kT288x256 ? 2 : -1;
-  CV_REQUIRE(i >= 0, CULLAVO_EINVAL, "tile rate: mode must be 2, 3 or 10");
-  CV_REQUIRE(i != 0 || tflops > 0.f, CULLAVO_EINVAL, "tile rate: mode 2 cannot be removed");
-  if (previous) *previous = (float)g_tile_rate[i];
-  g_tile_rate[i] = tflops > 0.f ? (double)tflops : 0.0;
-  return CULLAVO_OK;
-}
-
 // A/B switch for the precomputed-offset LDS-DMA loop of the 8-wave 256-row kernels
 extern "C" int cullavo_gemm_set_dma(int precomputed) {
   const int prev = g_dma_pre;
@@ -876,16 +701,12 @@ extern "C" int cullavo_gemm_set_dma(int precomputed) {
   return prev;
 }
 
-// A/B switch for the LDS-staged epilogue of the 8-wave kernels (1 = on, the default)
-extern "C" int cullavo_gemm_set_epilogue(int lds_staged) {
-  const int prev = (g_epi_lds & 1) | (g_nt_store << 1) | (g_epi_lds & 508) | (g_short288 ? 0 : 512);
-  g_epi_lds = lds_staged & 509;  // bit 0 LDS-staged; bits 2 / 3 / 4 disable its bias-residual / plain /
-                                 // activation + SwiGLU-backward paths; bit 5 the persistent forward kernel;
-                                 // bit 6 the prefetching SwiGLU-backward instantiation; bit 7 the direct
-                                 // (register) epilogue of the lean cases; bit 8 the persistent 288-row
-                                 // direct forward kernel (opt-in)
-  g_short288 = !((lds_staged >> 9) & 1);  // bit 9: no 288-row tiles at K < 2048 (round 5's plan)
-  g_nt_store = (lds_staged >> 1) & 1;
+// The 16-B epilogues of the 8-wave kernels (direct or LDS-staged; 1, the default) or per-lane 8-B
+// stores (0). Every other value selected an A/B variant that was measured and removed in ABI 9
+// (profiles/r05/gemm/epilogue/, profiles/r06/gemm/epi_ab.txt): it leaves the setting
+extern "C" int cullavo_gemm_set_epilogue(int on) {
+  const int prev = g_epi_lds;
+  if (on == 0 || on == 1) g_epi_lds = on;
   return prev;
 }
 
@@ -1006,12 +827,9 @@ static int gemm_impl(const cullavo_gemm_desc& d, void* stream, int tile_hint) {
   p.group_m = g_group_m;
   {
     auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    p.epi_lds = a16(d.C) && a16(d.bias) && a16(d.preact) && a16(residual) && a16(d.addend) &&
-                        (d.addend == nullptr || d.ld_addend % 8 == 0) && (g_epi_lds & 1)
-                    ? g_epi_lds
-                    : 0;
+    p.epi_lds = g_epi_lds && a16(d.C) && a16(d.bias) && a16(d.preact) && a16(residual) && a16(d.addend) &&
+                (d.addend == nullptr || d.ld_addend % 8 == 0);
   }
-  p.nt_store = g_nt_store;
   p.dma_pre = g_dma_pre && (a_layout == 1 || K % BK == 0) && (b_layout == 1 || K % BK == 0);
   p.lora_u = nullptr;
   p.lora_b = nullptr;
@@ -1067,9 +885,9 @@ static int gemm_impl(const cullavo_gemm_desc& d, void* stream, int tile_hint) {
     return f32 ? launch<1, 1, CULLAVO_DT_F32, 2>(p, s) : launch<1, 1, CULLAVO_DT_BF16, 2>(p, s);
   }
   // the SwiGLU-backward dX (act 3, bf16, LDS epilogue on, not split): its own instantiation with the
-  // prefetching epilogue (lds_epilogue_swiglu); cullavo_gemm_set_epilogue bit 6 keeps the general path
-  if (act == CULLAVO_ACT_SWIGLU_BWD && !f32 && p.epi_lds && p.part == nullptr && !(g_epi_lds & 64) &&
-      a_layout == 0 && (tile == kT288x256 || tile == kT256x256)) {
+  // prefetching epilogue (lds_epilogue_swiglu)
+  if (act == CULLAVO_ACT_SWIGLU_BWD && !f32 && p.epi_lds && p.part == nullptr && a_layout == 0 &&
+      (tile == kT288x256 || tile == kT256x256)) {
     if (tile == kT288x256)
       return b_layout == 0 ? launch256<0, 0, CULLAVO_DT_BF16, 288, 256, false, true>(p, s)
                            : launch256<0, 1, CULLAVO_DT_BF16, 288, 256, false, true>(p, s);
@@ -1077,7 +895,7 @@ static int gemm_impl(const cullavo_gemm_desc& d, void* stream, int tile_hint) {
                          : launch256<0, 1, CULLAVO_DT_BF16, 256, 256, false, true>(p, s);
   }
   if (tile == kT288x256) {  // a_layout 0 (above), one loader wave per SIMD
-    if (!f32 && b_layout == 0 && g_persist) {
+    if (!f32 && b_layout == 0) {
       const int rc = launch288pd(p, s);
       if (rc != -1) return rc;
     }
@@ -1097,8 +915,7 @@ static int gemm_impl(const cullavo_gemm_desc& d, void* stream, int tile_hint) {
   if (tile == kT256x256) {
 #define L256(AL, BL) \
   return f32 ? launch256<AL, BL, CULLAVO_DT_F32, 256, 256>(p, s) : launch256<AL, BL, CULLAVO_DT_BF16, 256, 256>(p, s);
-    if (a_layout == 0 && b_layout == 0 && !f32 && g_persist && p.part == nullptr && p.epi_lds && p.dma_pre &&
-        !(g_epi_lds & 32)) {
+    if (a_layout == 0 && b_layout == 0 && !f32 && p.part == nullptr && p.epi_lds && p.dma_pre) {
       const int rc = launch256p(p, s);
       if (rc != -1) return rc;
     }
@@ -1154,9 +971,10 @@ extern "C" int cullavo_gemm_ex(const cullavo_gemm_desc* desc, void* stream) {
   return gemm_impl(*desc, stream);
 }
 
-// A/B switch for the M-tail split of the automatic plan (1 = on, the default); returns the previous
+// A/B switch for the M-tail and round splits of the automatic plan (non-zero = on, the default);
+// returns the previous setting, 0 or 1
 extern "C" int cullavo_gemm_set_msplit(int on) {
   const int prev = g_msplit;
-  g_msplit = on == 2 ? 2 : on ? 1 : 0;
+  g_msplit = on != 0;
   return prev;
 }

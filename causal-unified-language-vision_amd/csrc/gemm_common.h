@@ -32,12 +32,12 @@ struct GemmArgs {
   uint64_t drop_seed;
   float* part;        // split-K: f32 partials [gridDim.y][M][N] (register-staged kernel only)
   int kt_per;         // K-tiles per split
-  int epi_lds;        // 8-wave kernels: LDS-staged 16-B epilogue (all pointers 16-B aligned)
-  int nt_store;       // C written with non-temporal stores (streamed past the caches)
+  int epi_lds;        // 8-wave kernels, 0 / 1: the LDS-staged or direct 16-B epilogue is allowed (every
+                      // pointer 16-B aligned)
+  int dma_pre;        // 8-wave 256-row kernels: per-lane DMA offsets precomputed, K advance in soffset
   int sk_dp;          // 8-wave kernels: tiles in the grid (the XCD remap's block count)
   int group_m;        // 8-wave tile order: > 0 groups of group_m M-tiles sweep N; < 0 groups of
                       // -group_m N-tiles sweep M
-  int dma_pre;        // 8-wave 256-row kernels: per-lane DMA offsets precomputed, K advance in soffset
   // fused LoRA up-projection (gemm256_k<..., LORA = true>): t = round(lora_scale * u_m B_m^T) for
   // the module m = n / lora_out of each output column, added to round(alpha*acc + bias)
   const u16* lora_u;  // [M, n_mod * 64] (row stride ld_lu): lora_A outputs of the group's modules
@@ -47,10 +47,18 @@ struct GemmArgs {
   float lora_scale;
 };
 
-template <typename V>
-DEV void st_c(const GemmArgs& p, V* dst, const V& v) {
-  if (p.nt_store) __builtin_nontemporal_store(v, dst);
-  else *dst = v;
+// The lean epilogue case of a bf16-output product: 0 plain (o = bf16(alpha acc)), 1 bias and / or
+// residual, 2 activation after an optional bias; -1: the general path (store8's per-option chain).
+// One rule for the host's kernel choice (gemm.hip launch256p, launch288pd, launch256_lean) and the
+// device's loop choice (lds_epilogue); direct_epilogue's MODE is the same number.
+__host__ __device__ inline int lean_case(const GemmArgs& p) {
+  const bool lean = p.act == CULLAVO_ACT_NONE && p.preact == nullptr && p.addend == nullptr && p.beta == 0.f &&
+                    p.drop_mode != 3;
+  if (lean) return p.bias == nullptr && p.residual == nullptr ? 0 : 1;
+  if (p.act != CULLAVO_ACT_NONE && p.act != CULLAVO_ACT_SWIGLU_BWD && p.preact == nullptr && p.addend == nullptr &&
+      p.residual == nullptr && p.beta == 0.f && p.drop_mode != 3)
+    return 2;
+  return -1;
 }
 
 // ---- LDS images -----------------------------------------------------------------------------
@@ -289,7 +297,7 @@ DEV void store4(const GemmArgs& p, const f32x4& acc, int64_t m, int64_t n) {
     u16x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = f2bf(v[j]);
-    st_c(p, reinterpret_cast<u16x4*>(cp), o);
+    *reinterpret_cast<u16x4*>(cp) = o;
   } else {
     float* cp = (float*)p.C + m * p.ldc + n;
     f32x4 o;
@@ -301,7 +309,7 @@ DEV void store4(const GemmArgs& p, const f32x4& acc, int64_t m, int64_t n) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = v[j];
     }
-    st_c(p, reinterpret_cast<f32x4*>(cp), o);
+    *reinterpret_cast<f32x4*>(cp) = o;
   }
 }
 
@@ -365,7 +373,7 @@ DEV void store8(const GemmArgs& p, const float (&a)[8], int64_t m, int64_t n) {
     u16x8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = f2bf(v[j]);
-    st_c(p, reinterpret_cast<u16x8*>(cp), o);
+    *reinterpret_cast<u16x8*>(cp) = o;
   } else {
     float* cp = (float*)p.C + m * p.ldc + n;
     f32x4 o0, o1;
@@ -377,8 +385,8 @@ DEV void store8(const GemmArgs& p, const float (&a)[8], int64_t m, int64_t n) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) { o0[j] = v[j]; o1[j] = v[4 + j]; }
     }
-    st_c(p, reinterpret_cast<f32x4*>(cp), o0);
-    st_c(p, reinterpret_cast<f32x4*>(cp + 4), o1);
+    *reinterpret_cast<f32x4*>(cp) = o0;
+    *reinterpret_cast<f32x4*>(cp + 4) = o1;
   }
 }
 
@@ -388,67 +396,6 @@ DEV void store8(const GemmArgs& p, const float (&a)[8], int64_t m, int64_t n) {
 // 8 contiguous columns each, so every global access is a full-width 16-B access and 32 lanes
 // cover one 512-B output row (the per-lane 8-B stores of the MFMA layout touch 16 rows per
 // instruction; measured +3-4 % on the whole GEMM, tools/lab/gemm_lab.hip).
-// the LDS epilogue's path for this product (lds_epilogue's cases): 0 plain, 1 bias and / or residual,
-// 2 activation, 3 SwiGLU backward, 4 the general store8
-template <int CT>
-DEV int lds_epi_mode(const GemmArgs& p) {
-  const bool lean = CT == CULLAVO_DT_BF16 && p.act == CULLAVO_ACT_NONE && p.preact == nullptr &&
-                    p.addend == nullptr && p.beta == 0.f && p.drop_mode != 3 && !p.nt_store;
-  if (lean && p.bias == nullptr && p.residual == nullptr && !(p.epi_lds & 8)) return 0;
-  if (lean && !(p.epi_lds & 4) && !(p.bias == nullptr && p.residual == nullptr)) return 1;
-  if (CT == CULLAVO_DT_BF16 && p.act != CULLAVO_ACT_NONE && p.act != CULLAVO_ACT_SWIGLU_BWD && p.preact == nullptr &&
-      p.addend == nullptr && p.residual == nullptr && p.beta == 0.f && p.drop_mode != 3 && !p.nt_store &&
-      !(p.epi_lds & 16))
-    return 2;
-  if (CT == CULLAVO_DT_BF16 && p.act == CULLAVO_ACT_SWIGLU_BWD && !(p.epi_lds & 16)) return 3;
-  return 4;
-}
-
-// one 8-column group of the LDS epilogue by mode (the arithmetic of store8 in every case)
-template <int CT>
-DEV void lds_store_item(const GemmArgs& p, float (&v)[8], int64_t m, int64_t n, int mode) {
-  if (mode == 4) {
-    store8<CT>(p, v, m, n);
-    return;
-  }
-  if (m >= p.M || n >= p.N) return;
-  if (mode == 3) {
-    swiglu_bwd_store<8>(p, v, m, n);
-    return;
-  }
-  float b[8], rs[8];
-  if (mode != 0 && p.bias) {
-    const u16x8 bv = *reinterpret_cast<const u16x8*>(p.bias + n);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) b[j] = bf2f(bv[j]);
-  }
-  if (mode == 1 && p.residual) {
-    const u16x8 rv = *reinterpret_cast<const u16x8*>(p.residual + m * p.ldr + n);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) rs[j] = bf2f(rv[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float x = v[j] * p.alpha;
-    if (mode != 0 && p.bias) x += b[j];
-    if (mode == 2) x = round_bf(x);
-    if (mode == 1 && p.residual) x = round_bf(x) + rs[j];
-    v[j] = x;
-  }
-  if (mode == 2) {
-    if (p.act == CULLAVO_ACT_QUICK_GELU) {
-      quick_gelu8(v);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = act_apply(p.act, v[j]);
-    }
-  }
-  u16x8 o;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = f2bf(v[j]);
-  *reinterpret_cast<u16x8*>(reinterpret_cast<u16*>(p.C) + m * p.ldc + n) = o;
-}
-
 // item i of a half's LDS image: 8 consecutive f32 outputs of one row (thread idx = tid + 512 i:
 // row idx >> 5, columns (idx & 31) * 8 ..), and their coordinates
 template <int R>
@@ -539,20 +486,17 @@ DEV void lds_epilogue(const GemmArgs& p, f32x4 (&acc)[TMW][TN], char* smem, int6
                       int wn, int lane) {
   static_assert(TN == 4, "256-column tiles");
   constexpr int R = BM2 / 2;
-  // plain bf16 outputs (no bias / addend / activation / residual / beta / output dropout / nt: the
+  // plain bf16 outputs (no bias / addend / activation / residual / beta / output dropout: the
   // q|k|v, gate|up and lm_head products, every dX without a residual and every dW): store8's
   // arithmetic reduces to o = bf16(alpha * acc), written by a lean loop. The general store8 path
   // (runtime-checked epilogue options per 8 columns) measured ~1/4 of a K = 1024 product and ~1/10
   // of a K = 4096 one (tools/lab/gemm256p_lab.hip, profiles/r05/gemm/persistent_lab.txt).
   // bias_res: the same with an optional bias and / or residual (the o_proj / down_proj forward,
   // the ViT's biased products): store8's v = alpha acc + bias, then bf16(bf16(v) + residual)
-  // (epi_lds bits 2 / 3: A/B switches that send these cases to the general path)
-  const bool lean = CT == CULLAVO_DT_BF16 && p.act == CULLAVO_ACT_NONE && p.preact == nullptr &&
-                    p.addend == nullptr && p.beta == 0.f && p.drop_mode != 3 && !p.nt_store;
-  const bool plain = lean && p.bias == nullptr && p.residual == nullptr && !(p.epi_lds & 8);
-  const bool bias_res = lean && !plain && !(p.epi_lds & 4);
-  // (unrolled activation / SwiGLU-backward paths here measured a slower 7B step: every 8-wave
-  // kernel carried their code -- the persistent forward kernel has them per instantiation)
+  // (lean_case 0 and 1; unrolled activation / SwiGLU-backward loops here measured a slower 7B step,
+  // every 8-wave kernel carried their code: those cases take the general path below)
+  const int lc = CT == CULLAVO_DT_BF16 ? lean_case(p) : -1;
+  const bool plain = lc == 0, bias_res = lc == 1;
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
     if (wm == half) {
@@ -634,7 +578,7 @@ DEV void lds_epilogue(const GemmArgs& p, f32x4 (&acc)[TMW][TN], char* smem, int6
 // The stores are buffer stores on C's descriptor: an out-of-range row or column gets an offset past
 // num_records and is dropped, so every wave always issues exactly 2 TMW store instructions (the
 // persistent kernel counts them in its vmcnt). MODE: 0 plain, 1 bias and / or residual, 2 activation
-// (after an optional bias) -- lds_epi_mode's cases 0-2, in store8's arithmetic (bitwise).
+// (after an optional bias) -- lean_case's cases 0-2, in store8's arithmetic (bitwise).
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4e;
 
 DEV unsigned pk_bf2(float a, float b) { return (unsigned)f2bf(a) | ((unsigned)f2bf(b) << 16); }
@@ -927,12 +871,6 @@ DEV void tile_mfma(const char* cur_c, int wm, int wn, int lane, f32x4 (&acc)[TMW
   }
 }
 
-// LDR selects which waves stage the next K-tile: 0 = all eight (each wave issues its share of
-// LDS-DMA pieces before its MFMAs, so both waves of a SIMD stall on DMA issue together);
-// 1 = waves 0-3 only, 2 = waves 4-7 only (one loader per SIMD: its DMA issue runs beside the
-// partner wave's MFMAs instead of beside nothing).
-// One tile's K-tiles [kb, ke) into acc (zeroed here): LDS-DMA double buffer, one barrier per
-// K-tile, the MFMA loop of the 8-wave kernels (shared by the data-parallel and stream-K kernels)
 // the fused LoRA's operand tiles (module m = n0 / lora_out): u rows m0.. at column block 64 m and
 // lora_B rows n0.., as a 64-deep layout-0 A / B image pair at lds (all eight waves issue)
 template <int BM2, int BN>
@@ -944,6 +882,11 @@ DEV void lora_stage(const GemmArgs& p, int64_t m0, int64_t n0, char* lds, int wa
   dma_tile<0, BN, 8>(rbl, 64, n0, p.N, 0, 64, lds + BM2 * BK * 2, wave, lane);
 }
 
+// One tile's K-tiles [kb, ke) into acc (zeroed here): LDS-DMA double buffer, one barrier per
+// K-tile, the MFMA loop of the data-parallel 8-wave kernels.
+// LDR = 1: waves 0-3 stage the next K-tile (one loader per SIMD, its DMA issue beside the partner
+// wave's MFMAs; all eight or waves 4-7 loading measured slower and removed, profiles/r03/ldr/). The
+// parameter stays because the kernels' names carry it.
 // LPF (the fused-LoRA kernels, gemm.hip lora_fuse): the last K-tile's iteration stages the
 // adapters' u rows and lora_B rows (a 64-deep layout-0 tile pair) into the stage it frees, so they
 // land under the last MFMAs; returns that stage's offset (-1 when not staged)
@@ -953,6 +896,7 @@ DEV int tile_k_range(const GemmArgs& p, __amdgpu_buffer_rsrc_t ra, __amdgpu_buff
   constexpr int TILE_A = BM2 * BK * 2;
   constexpr int TILE_B = BN * BK * 2;
   constexpr int STAGE = TILE_A + TILE_B;
+  static_assert(LDR == 1, "waves 0-3 load");
   const int wm = wave >> 2, wn = wave & 3;
 #pragma unroll
   for (int i = 0; i < TMW; ++i)
@@ -965,19 +909,18 @@ DEV int tile_k_range(const GemmArgs& p, __amdgpu_buffer_rsrc_t ra, __amdgpu_buff
   __syncthreads();
 
   if (p.dma_pre) {
-    constexpr int NWL = LDR == 0 ? 8 : 4;
-    const int lw = LDR == 0 ? wave : (wave & 3);
-    const bool loader = LDR == 0 || (LDR == 1 ? wave < 4 : wave >= 4);
-    unsigned va[dma_per<BM2, NWL>()], vb[dma_per<BN, NWL>()];
-    dma_prep<AL, BM2, NWL>(p.lda, m0, p.M, lw, lane, va);
-    dma_prep<BL, BN, NWL>(p.ldb, n0, p.N, lw, lane, vb);
+    const int lw = wave & 3;
+    const bool loader = wave < 4;
+    unsigned va[dma_per<BM2, 4>()], vb[dma_per<BN, 4>()];
+    dma_prep<AL, BM2, 4>(p.lda, m0, p.M, lw, lane, va);
+    dma_prep<BL, BN, 4>(p.ldb, n0, p.N, lw, lane, vb);
     for (int kt = kb; kt < ke; ++kt) {
       char* cur = smem + ((kt - kb) & 1) * STAGE;
       char* nxt = smem + ((kt - kb + 1) & 1) * STAGE;
       const int64_t k1 = (int64_t)(kt + 1) * BK;
       if (kt + 1 < ke && loader) {
-        dma_issue<BM2, NWL>(ra, va, dma_soff<AL>(k1, p.lda), nxt, lw);
-        dma_issue<BN, NWL>(rb, vb, dma_soff<BL>(k1, p.ldb), nxt + TILE_A, lw);
+        dma_issue<BM2, 4>(ra, va, dma_soff<AL>(k1, p.lda), nxt, lw);
+        dma_issue<BN, 4>(rb, vb, dma_soff<BL>(k1, p.ldb), nxt + TILE_A, lw);
       }
       if constexpr (LPF) {
         if (kt + 1 == ke) lora_stage<BM2, BN>(p, m0, n0, nxt, wave, lane);
@@ -1001,18 +944,10 @@ DEV int tile_k_range(const GemmArgs& p, __amdgpu_buffer_rsrc_t ra, __amdgpu_buff
     const int64_t k1 = (int64_t)(kt + 1) * BK;
     // next K-tile's LDS-DMA pieces, all issued before this tile's MFMAs (issuing them one by
     // one between MFMA groups measured 5-15 % slower, profiles/r01/gemm_8phase.md)
-    if (more) {
-      if constexpr (LDR == 0) {
-        dma_tile<AL, BM2, 8>(ra, p.lda, m0, p.M, k1, p.K, nxt, wave, lane);
-        dma_tile<BL, BN, 8>(rb, p.ldb, n0, p.N, k1, p.K, nxt + TILE_A, wave, lane);
-      } else {
-        const bool loader = LDR == 1 ? wave < 4 : wave >= 4;
-        if (loader) {
-          const int lw = wave & 3;
-          dma_tile<AL, BM2, 4>(ra, p.lda, m0, p.M, k1, p.K, nxt, lw, lane);
-          dma_tile<BL, BN, 4>(rb, p.ldb, n0, p.N, k1, p.K, nxt + TILE_A, lw, lane);
-        }
-      }
+    if (more && wave < 4) {
+      const int lw = wave & 3;
+      dma_tile<AL, BM2, 4>(ra, p.lda, m0, p.M, k1, p.K, nxt, lw, lane);
+      dma_tile<BL, BN, 4>(rb, p.ldb, n0, p.N, k1, p.K, nxt + TILE_A, lw, lane);
     }
     tile_mfma<AL, BL, BM2, BN, TMW, TN>(cur, wm, wn, lane, acc);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -56,10 +56,13 @@ extern "C" {
    attention and GEMV variants removed with them: the attention backward's staging setter, the
    decode GEMV's non-temporal-load setter, and the retired values of cullavo_attn_set_stage /
    cullavo_attn_set_bwd_tiles; 7: the supervised-row entry points cullavo_rmsnorm_fwd_rows,
-   cullavo_rmsnorm_bwd_rows and cullavo_rows_scatter added; 8: cullavo_attn_fwd_cached added). cullavo_sample_token
+   cullavo_rmsnorm_bwd_rows and cullavo_rows_scatter added; 8: cullavo_attn_fwd_cached added; 9: the
+   switches of the measured-slower GEMM variants removed with them: cullavo_gemm_set_splitk_target,
+   cullavo_gemm_set_tile_rate, every value of cullavo_gemm_set_epilogue but 0 and 1, and the second
+   mode of cullavo_gemm_set_msplit). cullavo_sample_token
    was added under 8 without a bump, as cullavo_lora_dx was under its version: a pure addition that
    changes no existing signature. A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
-#define CULLAVO_ABI_VERSION 8
+#define CULLAVO_ABI_VERSION 9
 
 int cullavo_abi_version(void);
 const char* cullavo_last_error(void);
@@ -159,44 +162,28 @@ int cullavo_lora_dx(int n_mod, int64_t M, int64_t N, const void* du, int64_t ld_
 
 /* Kernel-shape selection for cullavo_gemm: -1 = automatic (default), 0 = 128x128 tile /
  * 4 waves (register staged), 2 = 256x256 / 8 waves, 3 = 192x256 / 8 waves, 10 = 288x256 / 8 waves
- * (LDS-DMA staged; 3 and 10 fall back to 2 when A is not K-contiguous; 10 is chosen automatically
- * only for K >= 2048). Other values select automatic. The measured-slower variants of earlier
+ * (LDS-DMA staged; 3 and 10 fall back to 2 when A is not K-contiguous). Other values select
+ * automatic. The measured-slower variants of earlier
  * rounds (ping-pong / 8-phase, BK = 32 4-stage, 256x128, other loader waves, the round-5 4-wave
  * 256x256 kernel) are not in the library (ABI 4; tools/lab).
  * Returns the previous mode. For tests and tuning; not thread-safe. */
 int cullavo_gemm_set_tile(int mode);
-/* Per-tile rate (TFLOP/s) the automatic kernel-shape choice assumes for tile mode 2, 3 or 10
-   (its time model: FLOPs / rate x whole rounds of tiles over the CUs); rate <= 0 removes the
-   shape from the automatic choice (0 on mode 10 = round-2 behaviour). *previous (nullable)
-   receives the old rate. Tuning/A-B switch; not thread-safe. */
-int cullavo_gemm_set_tile_rate(int mode, float tflops, float* previous);
-/* M-tail split of the automatic plan (tuning/A-B switch, 1 = on, the default): when M is just past
-   a multiple of the chosen tile height, the head rows run on that tile in whole rounds and the
-   remaining rows as a second, thin product (split over K when cullavo_gemm_workspace sized the
-   caller's workspace for it). 2 (the default since round 6) = split wherever the plan's model
-   estimates a gain; 1 = only where it estimates >= 5 % (round 5). Returns the previous setting. */
+/* M-tail and round splits of the automatic plan (tuning/A-B switch; 0 = off, any other value = on,
+   the default): when M is just past a multiple of the chosen tile height, or past whole rounds of
+   tiles over the CUs, the head rows run on that tile in whole rounds and the remaining rows as a
+   second product (split over K when cullavo_gemm_workspace sized the caller's workspace for it),
+   wherever the plan's model estimates a gain. Returns the previous setting, 0 or 1. */
 int cullavo_gemm_set_msplit(int on);
 /* Tile order of the 8-wave kernels (tuning/A-B switch): > 0 = groups of that many M-tiles
    sweep the N-tiles, < 0 = groups of -group N-tiles sweep the M-tiles (default -4); each XCD
    walks a contiguous run of the order. 0 leaves the setting. Returns the previous setting. */
 int cullavo_gemm_set_group(int group);
-/* Split-K plan of the small-grid GEMMs (tuning/A-B switch): the number of blocks a split-K
-   launch aims for (default 512 = two 4-wave blocks per CU); out-of-range values leave it.
-   Returns the previous setting. */
-int cullavo_gemm_set_splitk_target(int blocks);
-/* Tuning/A-B switch. Bit 0: 1 (default) = the 8-wave kernels stage their epilogue through LDS
-   and store 16-B groups of 8 columns; 0 = per-lane 8-B stores straight from the MFMA layout.
-   Bit 1: C is written with non-temporal (streaming) stores. Bits 2 / 3 / 4 (round 5, A/B): send
-   the LDS epilogue's lean bias/residual, plain-output and activation / SwiGLU-backward paths to
-   the general per-option path (same values). Bit 5: no persistent forward kernel. Round 6, A/B
-   (same values): bit 6 keeps the SwiGLU-backward dX on the general epilogue path instead of its
-   prefetching instantiation; bit 7 keeps the LDS-staged epilogue for the lean cases instead of
-   the direct (register, 16-B buffer store) epilogue and its persistent forward kernel; bit 8 opts
-   into the persistent 288-row direct forward kernel at K >= 2048 and N > 2048 (elsewhere it is the
-   default);
-   bit 9 keeps the plan off 288-row tiles at K < 2048 (round 5's plan; the default takes them).
-   Returns the previous setting. */
-int cullavo_gemm_set_epilogue(int lds_staged);
+/* Tuning/A-B switch. 1 (default) = the 8-wave kernels write C in 16-B groups of 8 columns (the direct
+   register epilogue of the plain / bias / residual / activation products and the persistent forward
+   kernel built on it, the LDS-staged epilogue otherwise); 0 = per-lane 8-B stores straight from the
+   MFMA layout (same values). Any other value selected a variant that was measured and removed with
+   ABI 9: it leaves the setting as it is. Returns the setting before the call, 0 or 1. */
+int cullavo_gemm_set_epilogue(int on);
 /* Tuning/A-B switch for the 8-wave 256-row kernels: 1 = per-lane LDS-DMA source offsets
    computed once per tile and the K advance passed as the scalar offset (used when K % 64 == 0
    or the operand is stored [K][rows], layout 1; the default); 0 = offsets recomputed per

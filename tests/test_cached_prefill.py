@@ -156,7 +156,8 @@ def test_attn_fwd_cached_argument_checks():
     with pytest.raises(Exception, match="head_dim must be 16, 32, 64 or 128"):
         _lib.call("attn_fwd_cached", None, 192, None, None, 192, 64 * 192, None, 192, None, 1, 2, 4, 8, 96, 1.0, None, 1,
                   None)
-    assert _lib.abi_version() == 8 and _lib.lib().cullavo_abi_version() == 8
+    # the entry point came with ABI 8; the library and the header agree on the current version
+    assert _lib.abi_version() >= 8 and _lib.lib().cullavo_abi_version() == _lib.abi_version()
 
 
 def test_cached_kernel_lds_reads_not_used_before_their_wait():

@@ -156,14 +156,18 @@ def test_gemm_round_split_weight_gradient():
 
 @pytest.mark.parametrize("act", ["gelu", "quick_gelu"])
 def test_gemm_epilogue_paths_bit_identical(tile_mode, act):
-    """The LDS-staged 16-B epilogue (packed quick_gelu) and the per-lane one compute the same
-    roundings in the same order, so every output (bias, LoRA addend, residual, preact, activation,
-    accumulate) is bit-identical."""
+    """The 16-B epilogues (packed quick_gelu) and the per-lane one compute the same roundings in the
+    same order, so every output is bit-identical: the general path (bias, LoRA addend, residual,
+    preact, activation, accumulate), and the lean cases (plain, bias, residual, bias + residual; no
+    addend / preact / beta) on every layout pair -- the lean loops of the LDS-staged epilogue on the
+    192-row tile and the (1,0) kernel, the direct epilogue elsewhere."""
     from cullavo_amd import _lib
     M, N, K = 520, 776, 320
     x, w, b = rnd((M, K), 31).to(DEV), rnd((N, K), 32, 0.1).to(DEV), rnd((N,), 33, 0.1).to(DEV)
     r, t = rnd((M, N), 34).to(DEV), rnd((M, N), 35, 0.05).to(DEV)
+    xt, wt = x.t().contiguous(), w.t().contiguous()
     code = ops().ACT_GELU if act == "gelu" else ops().ACT_QUICK_GELU
+    lean = [(al, bl, bias, res) for al, bl in ((0, 0), (0, 1), (1, 0)) for bias in (None, b) for res in (None, r)]
     outs = []
     for epi in (1, 0):
         prev = _lib.lib().cullavo_gemm_set_epilogue(epi)
@@ -171,11 +175,24 @@ def test_gemm_epilogue_paths_bit_identical(tile_mode, act):
             y, pre = ops().linear(x, w, b, act=code, residual=r, want_preact=True, addend=t)
             acc = rnd((N, K), 36, dtype=torch.float32).to(DEV)
             ops().linear_dw(y, x, acc, beta=1.0)
-            outs.append((y, pre, acc))
+            cs = []
+            for al, bl, bias, res in lean:
+                A, B = (xt if al else x), (wt if bl else w)
+                C = torch.full((M, N), float("nan"), dtype=BF, device=DEV)
+                ops().gemm(al, bl, M, N, K, A, A.stride(0), B, B.stride(0), C, N, bias=bias, residual=res,
+                           ldr=N if res is not None else 0)
+                cs.append(C)
+            outs.append((y, pre, acc, *cs))
         finally:
             _lib.lib().cullavo_gemm_set_epilogue(prev)
     for a, c in zip(outs[0], outs[1]):
         assert torch.equal(a, c)
+    ref = x.float() @ w.float().T
+    for (al, bl, bias, res), C in zip(lean, outs[0][3:]):
+        z = ref + (bias.float() if bias is not None else 0)
+        if res is not None:
+            z = z.to(BF).float() + res.float()
+        close(C, z, 8e-3, f"lean epilogue {al}{bl} bias={bias is not None} res={res is not None}")
 
 
 @pytest.mark.parametrize("M,N,K,al,bl,tile,epi", [
@@ -186,13 +203,15 @@ def test_gemm_epilogue_paths_bit_identical(tile_mode, act):
     (2000, 1032, 1000, 0, 1, 2, "res"), (1032, 2056, 2000, 1, 1, 2, "plain"), (1032, 2056, 2000, 1, 1, 2, "res"),
     # > 256 tiles: the persistent kernel walks several tiles per CU (early K-tile 1 DMA, counted vmcnt)
     (8704 + 37, 4104, 1024, 0, 0, 2, "bias_res"), (8704 + 37, 2056, 192, 0, 0, 2, "plain"),
-    (8704, 4096, 64, 0, 0, 2, "qgelu"), (8704 + 37, 4104, 1024, 0, 0, 2, "res")])
+    (8704, 4096, 64, 0, 0, 2, "qgelu"), (8704 + 37, 4104, 1024, 0, 0, 2, "res"),
+    # the same walk on 288-row tiles (K < 2048: the persistent 288-row kernel, vmcnt(18))
+    (8704 + 37, 4104, 1024, 0, 0, 10, "bias_res"), (8704 + 37, 4104, 1024, 0, 0, 10, "res"),
+    (8704 + 37, 2056, 192, 0, 0, 10, "plain"), (8704, 4096, 64, 0, 0, 10, "qgelu")])
 def test_gemm_direct_epilogue_bitwise(M, N, K, al, bl, tile, epi):
     """The direct epilogue (round 6: accumulators packed, permlane16-swapped and stored as 16-B buffer
     stores, no LDS round trip; the persistent forward kernel with the next tile's K-tile 1 issued
-    before the stores, and the data-parallel 288- / 256-row kernels) against the LDS-staged epilogue
-    (cullavo_gemm_set_epilogue bit 7) and the per-lane epilogue (bit 0 off): bitwise equal for every
-    lean case (plain, bias, residual, bias + residual, quick_gelu / erf-GELU after a bias), ragged M
+    before the stores, on 256- and 288-row tiles, and the data-parallel 288- / 256-row kernels)
+    against the per-lane epilogue (cullavo_gemm_set_epilogue(0)): bitwise equal for every lean case (plain, bias, residual, bias + residual, quick_gelu / erf-GELU after a bias), ragged M
     and N tiles included, and within bf16 noise of the fp32 product."""
     from cullavo_amd import _lib
     L = _lib.lib()
@@ -205,7 +224,7 @@ def test_gemm_direct_epilogue_bitwise(M, N, K, al, bl, tile, epi):
     prev_t, prev_e = L.cullavo_gemm_set_tile(tile), L.cullavo_gemm_set_epilogue(1)
     outs = []
     try:
-        for mode in (1, 1 | 128, 0, 1 | 256):  # default, LDS-staged, per-lane, persistent 288-row opt-in
+        for mode in (1, 0):  # the direct epilogue (default), per-lane stores
             L.cullavo_gemm_set_epilogue(mode)
             C = torch.full((M, N), float("nan"), dtype=BF, device=DEV)
             ops().gemm(al, bl, M, N, K, A, A.stride(0), B, B.stride(0), C, N, bias=bias, act=act, residual=res,
@@ -223,9 +242,7 @@ def test_gemm_direct_epilogue_bitwise(M, N, K, al, bl, tile, epi):
     if res is not None:
         ref = ref.to(BF).float() + res.float()
     close(outs[0], ref, 8e-3, f"direct epilogue {epi}")
-    assert torch.equal(outs[0], outs[1]), "direct vs LDS-staged epilogue"
-    assert torch.equal(outs[0], outs[2]), "direct vs per-lane epilogue"
-    assert torch.equal(outs[0], outs[3]), "direct vs the persistent 288-row direct kernel (opt-in)"
+    assert torch.equal(outs[0], outs[1]), "direct vs per-lane epilogue"
 
 
 @pytest.mark.parametrize("M,N,K,al,bl", [(2304, 8192, 1024, 0, 0), (1032, 2056, 4104, 1, 1), (2000, 1544, 520, 0, 1),
@@ -427,16 +444,6 @@ def test_swiglu_bwd_fused_in_dx_gemm(M, Fd, d, tile):
         _lib.lib().cullavo_gemm_set_tile(prev)
     assert torch.equal(fused, ref)
     assert torch.equal(fused_t, ref)
-    # the prefetching LDS-staged form (default) against the rolled general path (bit 6)
-    L = _lib.lib()
-    prev_t, prev_e = L.cullavo_gemm_set_tile(tile), L.cullavo_gemm_set_epilogue(1)
-    try:
-        for bits in (1 | 64,):
-            L.cullavo_gemm_set_epilogue(bits)
-            assert torch.equal(ops().linear_dx(dy, w, swiglu_gu=gu), ref), bits
-    finally:
-        L.cullavo_gemm_set_tile(prev_t)
-        L.cullavo_gemm_set_epilogue(prev_e)
     with pytest.raises(Exception):
         ops().linear_dx(dy, w, swiglu_gu=gu[:, :Fd])
 

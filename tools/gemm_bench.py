@@ -59,10 +59,9 @@ def main():
             for mode, grp in [(m.strip(), int(gg)) for m in a.modes.split(",") for gg in a.groups.split(",")]:
                 lib.cullavo_gemm_set_group(grp)
                 lane_epi = "L" in mode  # e.g. "-1L": same kernel, per-lane epilogue
-                nt = "N" in mode        # e.g. "-1N": non-temporal C stores
                 lib.cullavo_gemm_set_dma(0 if "D" in mode else 1)  # "-1D": per-K-tile DMA offsets
-                lib.cullavo_gemm_set_tile(int(mode.rstrip("LND")))
-                lib.cullavo_gemm_set_epilogue((0 if lane_epi else 1) | (2 if nt else 0))
+                lib.cullavo_gemm_set_tile(int(mode.rstrip("LD")))
+                lib.cullavo_gemm_set_epilogue(0 if lane_epi else 1)
                 o = ours[kind]()
                 err = ((o.float() - r.float()).norm() / r.float().norm()).item()
                 t = timeit(ours[kind], a.iters)
