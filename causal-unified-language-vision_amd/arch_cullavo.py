@@ -306,7 +306,8 @@ class CuLLaVOModel(nn.Module):
                  do_sample: bool = False, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
                  eos_token_id: int | None = None, pad_token_id: int | None = None, use_cache: bool = True,
                  generator=None, past_key_values=None, return_dict_in_generate: bool = False,
-                 prefill_chunk: int | None = None, seed: int | None = None, device_loop: bool | None = None, **kw):
+                 prefill_chunk: int | None = None, seed: int | None = None, device_loop: bool | None = None,
+                 compact_cache: bool = False, **kw):
         """Decoder-only generate: returns [B, S + new] (prompt ids then sampled ids), stopping when
         every sequence has produced eos_token_id (finished rows are padded with pad_token_id).
         past_key_values: the cache of an earlier call continues a conversation -- input_ids then holds
@@ -319,7 +320,17 @@ class CuLLaVOModel(nn.Module):
         sequence's stream id, the token's index): reproducible without a torch.Generator and, for a
         sequence, independent of its batch neighbours; the stream ids default to arange(B) and
         sample_offsets=<[B] ints> overrides them. device_loop=True alone decodes greedily on the
-        device. With neither argument the host loop around generation.sample_next runs unchanged."""
+        device. With neither argument the host loop around generation.sample_next runs unchanged.
+        compact_cache: keep the KV cache ragged and compact (generation.KVCache.lengths). Off, every
+        row appends one cache row per step, so a row that met eos early caches the pads it is fed
+        afterwards and its conversation cannot be continued correctly. On (host and device loop), a
+        row stops advancing with the step that would feed its eos: the returned cache
+        (return_dict_in_generate=True) holds, per row, every real token but the row's last one (its
+        eos, or the last sampled token of an unfinished row: HF's convention, per row), and the
+        sequences are those of compact_cache=False. generate(past_key_values=<that cache>,
+        input_ids=<the left-padded new turns>, attention_mask=<[B, S] or [B, past + S]>) then
+        continues every conversation; a ragged input cache or a left-padded new turn takes the
+        ragged path without the flag."""
         from .generation import KVCache, device_sampling, sample_next
         if not use_cache:
             raise NotImplementedError("generate() runs on the KV cache (use_cache=True)")
@@ -353,12 +364,15 @@ class CuLLaVOModel(nn.Module):
             out = self._forward_cached(input_ids, None, attention_mask, None, cache, None, cfg.vision_feature_layer,
                                        strategy, None, True, prefill_chunk=prefill_chunk)
         cache = out.past_key_values
-        if return_dict_in_generate:  # the cache's state before the first sampled token
+        compact = bool(compact_cache) or cache.lengths is not None
+        if compact:
+            cache.make_ragged()
+        elif return_dict_in_generate:  # the cache's state before the first sampled token
             len0, pos0 = cache.length, cache.next_pos.clone()
         logits = out.logits[:, -1]
         if on_device:
             gen = self._generate_on_device(cache, logits, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
-                                           eos_token_id, pad, kw)
+                                           eos_token_id, pad, kw, compact)
         else:
             finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
             new = []
@@ -366,7 +380,7 @@ class CuLLaVOModel(nn.Module):
             graph = None
             if kw.get("decode_graph", True) and max_new_tokens > 1 and input_ids.is_cuda:
                 from .generation import DecodeGraph
-                graph = DecodeGraph(self, cache)
+                graph = DecodeGraph(self, cache, live=compact)
             check_every = 16  # all-finished test every 16 tokens: one host sync per 16 steps, not per step
             for step in range(max_new_tokens):
                 tok = sample_next(logits, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
@@ -380,9 +394,12 @@ class CuLLaVOModel(nn.Module):
                 if step + 1 == max_new_tokens:
                     break
                 if graph is not None:
+                    if compact:  # a finished row (its eos included) is fed but does not advance
+                        graph.live.copy_(~finished)
                     logits = graph.step(tok)[:, -1]
                 else:
-                    out = self._forward_cached(tok[:, None], None, None, None, cache, None, cfg.vision_feature_layer,
+                    live = (~finished)[:, None].to(torch.long) if compact else None
+                    out = self._forward_cached(tok[:, None], None, live, None, cache, None, cfg.vision_feature_layer,
                                                cfg.vision_feature_select_strategy, None, True)
                     logits = out.logits[:, -1]
             gen = torch.stack(new, 1)
@@ -394,6 +411,12 @@ class CuLLaVOModel(nn.Module):
             if bool(all_done.any()):
                 gen = gen[:, :int(all_done.to(torch.int64).argmax()) + 1]
         sequences = torch.cat([input_ids, gen.to(input_ids.dtype)], 1)
+        if return_dict_in_generate and compact:
+            # per row, every real token but the row's last one is cached: no row advanced on a pad (the
+            # lengths and positions leave the decode graph's buffers)
+            cache.lengths, cache.next_pos = cache.lengths.clone(), cache.next_pos.clone()
+            cache.length = int(cache.lengths.max())
+            return CullavoGenerateOutput(sequences=sequences, past_key_values=cache)
         if return_dict_in_generate:
             # every returned token but the last is cached (rows a stopped batch ran past are dropped;
             # the positions leave the decode graph's buffer)
@@ -403,7 +426,7 @@ class CuLLaVOModel(nn.Module):
         return sequences
 
     def _generate_on_device(self, cache, logits, max_new_tokens: int, do_sample: bool, temperature, top_k, top_p,
-                            seed, eos_token_id, pad, kw):
+                            seed, eos_token_id, pad, kw, compact: bool = False):
         """generate()'s device loop: the first token by the sampling kernel on the prefill logits,
         every later one by a replay of the decode graph that ends with that kernel; the host reads
         `finished` every 16 replays and the tokens once at the end. Returns the new ids [B, n]."""
@@ -416,7 +439,7 @@ class CuLLaVOModel(nn.Module):
         state.sample(logits)
         graph = None
         if kw.get("decode_graph", True) and max_new_tokens > 1:
-            graph = DecodeGraph(self, cache, sampler=state)
+            graph = DecodeGraph(self, cache, sampler=state, live=compact)
         check_every = 16  # as the host loop: one host sync per 16 tokens
         n = 1
         while n < max_new_tokens:
@@ -425,7 +448,8 @@ class CuLLaVOModel(nn.Module):
             if graph is not None:
                 graph.advance()
             else:
-                out = self._forward_cached(state.next_ids[:, None], None, None, None, cache, None,
+                live = (state.finished == 0)[:, None].to(torch.long) if compact else None
+                out = self._forward_cached(state.next_ids[:, None], None, live, None, cache, None,
                                            cfg.vision_feature_layer, cfg.vision_feature_select_strategy, None, True)
                 state.sample(out.logits[:, -1])
             n += 1

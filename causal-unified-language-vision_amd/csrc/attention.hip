@@ -577,7 +577,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_k(const u16* __restrict_
                                                           u16* __restrict__ O, int64_t ldo,
                                                           float* __restrict__ LSE, int H, int Lq, int Lk,
                                                           float scale, const int32_t* __restrict__ kv_start) {
-  constexpr bool CACHED = false;
+  constexpr bool CACHED = false, RAGGED = false;
+  constexpr int qpad = 0;
 #include "attn_fwd_pipe_body.h"
 }
 
@@ -592,7 +593,30 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_cached_k(const u16* __restric
                                                             u16* __restrict__ O, int64_t ldo,
                                                             float* __restrict__ LSE, int H, int Lq, int Lk,
                                                             float scale, const int32_t* __restrict__ kv_start) {
-  constexpr bool CAUSAL = true, CACHED = true;
+  constexpr bool CAUSAL = true, CACHED = true, RAGGED = false;
+  constexpr int qpad = 0;
+#include "attn_fwd_pipe_body.h"
+}
+
+// attn_fwd_cached_k with a prefix length per sequence (cullavo_attn_fwd_ragged): the [B, Lq] query
+// block is left-padded, sequence b's first q_pad[b] rows are padding and its cache holds kv_len[b]
+// rows, the Lq - q_pad[b] new ones included. Query i >= q_pad[b] sits at cache row kv_len[b] - Lq +
+// i. Device values cannot be checked on the host: kv_len[b] is clamped to [0, cap] (cap = the rows
+// of a sequence's slab, ld_batch / ld_tok) and q_pad[b] to [0, Lq], so no value fetches outside the
+// slab. Both are loaded once per workgroup from a uniform address (scalar loads).
+template <int D>
+__global__ __launch_bounds__(256, 2) void attn_fwd_ragged_k(const u16* __restrict__ Q, int64_t ldq,
+                                                            const u16* __restrict__ K, int64_t ldk,
+                                                            const u16* __restrict__ V, int64_t ldv,
+                                                            u16* __restrict__ O, int64_t ldo,
+                                                            float* __restrict__ LSE, int H, int Lq, int cap,
+                                                            float scale, const int32_t* __restrict__ kv_start,
+                                                            const int32_t* __restrict__ kv_len,
+                                                            const int32_t* __restrict__ q_pad) {
+  constexpr bool CAUSAL = true, CACHED = true, RAGGED = true;
+  const int seq = xcd_remap(blockIdx.x, gridDim.x) / ((Lq + 127) / 128) / H;  // the body's b
+  const int Lk = min(max(kv_len[seq], 0), cap);
+  const int qpad = q_pad ? min(max(q_pad[seq], 0), Lq) : 0;
 #include "attn_fwd_pipe_body.h"
 }
 
@@ -1320,6 +1344,22 @@ int fwd_cached_launch(const u16* q, int64_t ldq, const u16* kc, const u16* vc, i
   return cullavo_check_launch("attn_fwd_cached");
 }
 
+template <int D>
+int fwd_ragged_launch(const u16* q, int64_t ldq, const u16* kc, const u16* vc, int64_t ld_tok, int64_t ld_batch,
+                      u16* o, int64_t ldo, float* lse, int B, int H, int Lq, int cap, float scale,
+                      const int32_t* ks, const int32_t* kv_len, const int32_t* q_pad, hipStream_t s) {
+  const int smem = 4 * 64 * D * 2;
+  static bool once = false;
+  if (!once) {
+    set_smem(attn_fwd_ragged_k<D>, smem);
+    once = true;
+  }
+  const unsigned grid = (unsigned)(cdiv(Lq, 128) * H * B);
+  attn_fwd_ragged_k<D><<<grid, 256, smem, s>>>(q, ldq, kc, ld_tok, vc, ld_batch, o, ldo, lse, H, Lq, cap, scale, ks,
+                                               kv_len, q_pad);
+  return cullavo_check_launch("attn_fwd_ragged");
+}
+
 // backward mode (cullavo_attn_set_bwd_tiles):
 //   0 = the 4-wave kernels, 32-row dK/dV tiles and 32-key dQ tiles (the plain pair);
 //   2 = as 0 with 64-key dQ tiles, bitwise equal to 0;
@@ -1449,6 +1489,36 @@ extern "C" int cullavo_attn_fwd_cached(const void* q, int64_t ldq, const void* k
   u16* O = (u16*)o;
   if (D == 128) return fwd_cached_launch<128>(Q, ldq, K, V, ld_tok, ld_batch, O, ldo, lse, B, H, Lq, past, scale, kv_start, s);
   return fwd_cached_launch<64>(Q, ldq, K, V, ld_tok, ld_batch, O, ldo, lse, B, H, Lq, past, scale, kv_start, s);
+}
+
+extern "C" int cullavo_attn_fwd_ragged(const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
+                                       int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B,
+                                       int H, int Lq, const int32_t* kv_len, const int32_t* q_pad, int D,
+                                       float scale, const int32_t* kv_start, int dtype, void* stream) {
+  CV_REQUIRE(dtype == CULLAVO_DT_BF16 || dtype == CULLAVO_DT_F32, CULLAVO_EUNSUPPORTED, "attention: bf16 / f32");
+  CV_REQUIRE(D == 16 || D == 32 || D == 64 || D == 128, CULLAVO_EUNSUPPORTED, "head_dim must be 16, 32, 64 or 128");
+  CV_REQUIRE(B >= 0 && H >= 0, CULLAVO_EINVAL, "B and H must not be negative");
+  CV_REQUIRE(Lq >= 1, CULLAVO_EINVAL, "attn_fwd_ragged: Lq must be at least 1");
+  CV_REQUIRE(kv_len != nullptr, CULLAVO_EINVAL, "attn_fwd_ragged: kv_len (the filled rows per sequence) is null");
+  CV_REQUIRE(ldq % 8 == 0 && ld_tok % 8 == 0 && ldo % 8 == 0, CULLAVO_EINVAL, "token strides must be multiples of 8");
+  CV_REQUIRE(ldq >= (int64_t)H * D && ld_tok >= (int64_t)H * D && ldo >= (int64_t)H * D, CULLAVO_EINVAL,
+             "token stride smaller than H*D");
+  CV_REQUIRE(ld_batch % 8 == 0, CULLAVO_EINVAL, "the cache's batch stride must be a multiple of 8");
+  CV_REQUIRE(ld_batch >= ld_tok, CULLAVO_EINVAL, "the cache's batch stride is smaller than one row");
+  if (B == 0 || H == 0) return CULLAVO_OK;
+  // the rows of a sequence's slab: the bound the kernel clamps kv_len[b] to
+  const int cap = (int)std::min<int64_t>(ld_batch / ld_tok, INT32_MAX - Lq);
+  hipStream_t s = CV_STREAM(stream);
+  if (dtype == CULLAVO_DT_F32 || D < 64)
+    return cullavo_attn_generic_fwd_ragged(q, ldq, k_cache, v_cache, ld_tok, ld_batch, o, ldo, lse, B, H, Lq, cap, D,
+                                           scale, kv_start, kv_len, q_pad, dtype, s);
+  const u16 *Q = (const u16*)q, *K = (const u16*)k_cache, *V = (const u16*)v_cache;
+  u16* O = (u16*)o;
+  if (D == 128)
+    return fwd_ragged_launch<128>(Q, ldq, K, V, ld_tok, ld_batch, O, ldo, lse, B, H, Lq, cap, scale, kv_start, kv_len,
+                                  q_pad, s);
+  return fwd_ragged_launch<64>(Q, ldq, K, V, ld_tok, ld_batch, O, ldo, lse, B, H, Lq, cap, scale, kv_start, kv_len,
+                               q_pad, s);
 }
 
 // default: D=128 (the LM) mode 7 -- in the 7B shape 532 us per layer against 667 for mode 4

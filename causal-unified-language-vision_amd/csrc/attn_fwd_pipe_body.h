@@ -10,6 +10,15 @@
 // capacity, not Lk rows). The LDS-DMA descriptors end at row Lk of the sequence's cache, so the
 // free rows behind it are never fetched: in a tile's tail they land as zeros and are masked like
 // any key >= Lk.
+//
+// RAGGED (attn_fwd_ragged_k, CAUSAL = CACHED = true): the kernel sets Lk = kv_len[b] and qpad =
+// q_pad[b] (both workgroup-uniform, scalar registers) before these statements, so every bound above
+// is the sequence's own. Queries q < qpad are padding: they load no Q row and see no key (kspan =
+// 0), which makes them the zero rows with lse = +inf of any query without a visible key; a query
+// tile wholly inside the padding runs no key tile (ntiles = 0: nothing is fetched), a tile that
+// holds some padding masks every key tile. past = Lk - Lq may be negative (a short cache behind a
+// long pad): queries below -past are padding by construction, kspan = 0 covers bad inputs. With
+// RAGGED = false, qpad is the constant 0 and every RAGGED term folds away.
   constexpr int KT = 64;
   constexpr int TILE = KT * D * 2;
   constexpr int NS = D / 16;  // k-steps over D: 8 (D = 128) or 4 (D = 64)
@@ -34,7 +43,7 @@
   frag8 qf[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
-    u16x8 v = (q < Lq) ? *reinterpret_cast<const u16x8*>(Qb + (int64_t)q * ldq + 16 * s + 8 * hf) : u16x8(0);
+    u16x8 v = (q < Lq && (!RAGGED || q >= qpad)) ? *reinterpret_cast<const u16x8*>(Qb + (int64_t)q * ldq + 16 * s + 8 * hf) : u16x8(0);
     qf[s] = __builtin_bit_cast(frag8, v);
   }
   f32x16 o[ND];
@@ -46,10 +55,11 @@
   // key position of this workgroup's first query: every key <= qlo is visible to all its queries
   const int qlo = past + qb * 128;
   const int khi = CAUSAL ? min(Lk, past + q + 1) : Lk;
-  const unsigned kspan = (unsigned)max(khi - kstart, 0);
+  const unsigned kspan = (RAGGED && q < qpad) ? 0u : (unsigned)max(khi - kstart, 0);
+  const bool qtile_pad = RAGGED && qb * 128 < qpad;  // the tile holds padding queries: mask every key tile
   int kend = Lk;
   if (CAUSAL) kend = min(Lk, qlo + 128);
-  const int ntiles = (kend + KT - 1) / KT;
+  const int ntiles = (RAGGED && qb * 128 + 128 <= qpad) ? 0 : (kend + KT - 1) / KT;
   const int t0 = kstart / KT;
 
   StageDMA1<KT, D, 4> dk_, dv_;
@@ -118,7 +128,7 @@
   float alpha_p = 1.f;  // the pending rescale of l, folded into the next row-sum add
   auto prep = [&](int t, f32x16 (&sp)[2]) {
     const int kbase = t * KT;
-    const bool need_mask = (CAUSAL && kbase + KT - 1 > qlo) || kbase + KT > Lk || kbase < kstart;
+    const bool need_mask = (CAUSAL && kbase + KT - 1 > qlo) || kbase + KT > Lk || kbase < kstart || qtile_pad;
     if (need_mask) {
       const int koff = kbase + 4 * hf - kstart;
       if (kbase >= kstart) {

@@ -36,84 +36,37 @@ DEV bool visible(int64_t qg, int64_t jg, int Lk, int ks, bool causal) {
 // Lq keys (query i sees keys <= past + i), K / V are one layer's KV cache, both with token stride
 // ldk, sequence b at element offset b * ldv (ldv carries the cache's batch stride); rows >= Lk of
 // the cache are never staged. lse may then be null.
+// RAGGED (cullavo_attn_fwd_ragged; CACHED, causal): Lk is sequence b's own kv_len[b] and the first
+// qpad = q_pad[b] queries of its left-padded block are padding -- they see no key (a zero row, lse =
+// +inf), and a query block wholly inside the padding stages no key block. Lk - Lq may be negative.
 template <typename T, int D, bool CACHED>
 __global__ __launch_bounds__(256) void attn_gen_fwd_k(const T* __restrict__ Q, int64_t ldq, const T* __restrict__ K,
                                                       int64_t ldk, const T* __restrict__ V, int64_t ldv,
                                                       T* __restrict__ O, int64_t ldo, float* __restrict__ LSE, int H,
                                                       int Lq, int Lk, float scale, int causal,
                                                       const int32_t* __restrict__ kv_start) {
-  constexpr int LD = D + 1;
-  extern __shared__ float sm[];
-  float* sQ = sm;
-  float* sK = sQ + QF * LD;
-  float* sV = sK + KB * LD;
-  float* sP = sV + KB * LD;  // [QF][KB + 1]
-  const int nqb = (int)cdiv(Lq, QF);
-  const int qb = blockIdx.x % nqb, h = (blockIdx.x / nqb) % H, b = blockIdx.x / (nqb * H);
-  const int q0 = qb * QF;
-  const int t = threadIdx.x, r = t >> 2, part = t & 3;
-  const int ks = kv_start ? kv_start[b] : 0;
-  const int64_t qg = q0 + r;
-  const int past = CACHED ? Lk - Lq : 0;
-  const int64_t qpos = past + qg;  // the query's key position
-  // sequence b's first K / V row: row b * Lk of the packed [B * Lk] rows, or of its own cache
-  const T* Kb = K + (CACHED ? (int64_t)b * ldv : 0) + h * D;
-  const T* Vb = V + (CACHED ? (int64_t)b * ldv : 0) + h * D;
-  const int64_t krow0 = CACHED ? 0 : (int64_t)b * Lk;
-  const int64_t ldvt = CACHED ? ldk : ldv;
-  stage_rows<T>(sQ, LD, Q + h * D, ldq, (int64_t)b * Lq + q0, min(QF, Lq - q0), QF, D);
-  float m = -INFINITY, l = 0.f;
-  float o[D / 4];
-#pragma unroll
-  for (int c = 0; c < D / 4; ++c) o[c] = 0.f;
-  const int kend = causal ? min(Lk, past + q0 + QF) : Lk;
-  for (int k0 = 0; k0 < kend; k0 += KB) {
-    __syncthreads();
-    stage_rows<T>(sK, LD, Kb, ldk, krow0 + k0, min(KB, Lk - k0), KB, D);
-    stage_rows<T>(sV, LD, Vb, ldvt, krow0 + k0, min(KB, Lk - k0), KB, D);
-    __syncthreads();
-    float s[KB / 4];
-    float bmax = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < KB / 4; ++i) {
-      const int j = part + 4 * i;
-      float acc = 0.f;
-      for (int d = 0; d < D; ++d) acc = fmaf(sQ[r * LD + d], sK[j * LD + d], acc);
-      s[i] = visible(qpos, k0 + j, Lk, ks, causal) && qg < Lq ? acc * scale : -INFINITY;
-      bmax = fmaxf(bmax, s[i]);
-    }
-    bmax = fmaxf(bmax, __shfl_xor(bmax, 1, 64));
-    bmax = fmaxf(bmax, __shfl_xor(bmax, 2, 64));
-    const float mnew = fmaxf(m, bmax);
-    const float alpha = mnew == -INFINITY ? 1.f : __expf(m - mnew);
-    float psum = 0.f;
-#pragma unroll
-    for (int i = 0; i < KB / 4; ++i) {
-      const float p = s[i] == -INFINITY ? 0.f : __expf(s[i] - mnew);
-      sP[r * (KB + 1) + part + 4 * i] = p;
-      psum += p;
-    }
-    psum += __shfl_xor(psum, 1, 64);
-    psum += __shfl_xor(psum, 2, 64);
-    l = l * alpha + psum;
-    m = mnew;
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < D / 4; ++c) o[c] *= alpha;
-    for (int j = 0; j < KB; ++j) {
-      const float p = sP[r * (KB + 1) + j];
-#pragma unroll
-      for (int c = 0; c < D / 4; ++c) o[c] = fmaf(p, sV[j * LD + part + 4 * c], o[c]);
-    }
-  }
-  if (qg < Lq) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-    T* op = O + ((int64_t)b * Lq + qg) * ldo + h * D;
-#pragma unroll
-    for (int c = 0; c < D / 4; ++c) Elt<T>::st(op, part + 4 * c, o[c] * inv);
-    if ((!CACHED || LSE != nullptr) && part == 0)
-      LSE[((int64_t)b * H + h) * Lq + qg] = l > 0.f ? m + __logf(l) : INFINITY;
-  }
+  constexpr bool RAGGED = false;
+  constexpr int qpad = 0;
+#include "attn_gen_fwd_body.h"
+}
+
+// kv_len[b] clamped to [0, cap] (cap: the rows of a sequence's slab) and q_pad[b] to [0, Lq]: device
+// values the host cannot check must not stage rows outside the slab
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_gen_fwd_ragged_k(const T* __restrict__ Q, int64_t ldq,
+                                                             const T* __restrict__ K, int64_t ldk,
+                                                             const T* __restrict__ V, int64_t ldv,
+                                                             T* __restrict__ O, int64_t ldo, float* __restrict__ LSE,
+                                                             int H, int Lq, int cap, float scale,
+                                                             const int32_t* __restrict__ kv_start,
+                                                             const int32_t* __restrict__ kv_len,
+                                                             const int32_t* __restrict__ q_pad) {
+  constexpr bool CACHED = true, RAGGED = true;
+  constexpr int causal = 1;
+  const int seq = blockIdx.x / ((int)cdiv(Lq, QF) * H);  // the body's b
+  const int Lk = min(max(kv_len[seq], 0), cap);
+  const int qpad = q_pad ? min(max(q_pad[seq], 0), Lq) : 0;
+#include "attn_gen_fwd_body.h"
 }
 
 // ---- backward -----------------------------------------------------------------------------------
@@ -312,6 +265,24 @@ int gen_fwd_cached(const void* q, int64_t ldq, const void* kc, const void* vc, i
 }
 
 template <typename T, int D>
+int gen_fwd_ragged(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ld_tok, int64_t ld_batch,
+                   void* o, int64_t ldo, float* lse, int B, int H, int Lq, int cap, float scale, const int32_t* ks,
+                   const int32_t* kv_len, const int32_t* q_pad, hipStream_t s) {
+  constexpr int LD = D + 1;
+  const int smem = (QF * LD + 2 * KB * LD + QF * (KB + 1)) * 4;
+  static bool once = false;
+  if (!once) {
+    (void)hipFuncSetAttribute((const void*)attn_gen_fwd_ragged_k<T, D>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              smem);
+    once = true;
+  }
+  const unsigned grid = (unsigned)(cdiv(Lq, QF) * H * B);
+  attn_gen_fwd_ragged_k<T, D><<<grid, 256, smem, s>>>((const T*)q, ldq, (const T*)kc, ld_tok, (const T*)vc, ld_batch,
+                                                      (T*)o, ldo, lse, H, Lq, cap, scale, ks, kv_len, q_pad);
+  return cullavo_check_launch("attn_fwd_ragged (generic)");
+}
+
+template <typename T, int D>
 int gen_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
             int64_t ldo, const void* dout, int64_t lddo, const float* lse, float* delta, void* dq, int64_t lddq,
             void* dk, int64_t lddk, void* dv, int64_t lddv, int B, int H, int Lq, int Lk, float scale, int causal,
@@ -379,6 +350,30 @@ int cullavo_attn_generic_fwd_cached(const void* q, int64_t ldq, const void* k_ca
   else { GCD(u16) }
 #undef GCD
 #undef GC
+  cullavo_set_error("attention: head_dim must be 16, 32, 64 or 128");
+  return CULLAVO_EUNSUPPORTED;
+}
+
+// Dispatch used by cullavo_attn_fwd_ragged (attention.hip) for f32 storage or D in {16, 32}.
+int cullavo_attn_generic_fwd_ragged(const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
+                                    int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B, int H,
+                                    int Lq, int cap, int D, float scale, const int32_t* ks, const int32_t* kv_len,
+                                    const int32_t* q_pad, int dtype, hipStream_t s) {
+#define GR(T_, D_)                                                                                                   \
+  return gen_fwd_ragged<T_, D_>(q, ldq, k_cache, v_cache, ld_tok, ld_batch, o, ldo, lse, B, H, Lq, cap, scale, ks, \
+                                kv_len, q_pad, s)
+#define GRD(T_)                  \
+  switch (D) {                   \
+    case 16: GR(T_, 16);         \
+    case 32: GR(T_, 32);         \
+    case 64: GR(T_, 64);         \
+    case 128: GR(T_, 128);       \
+    default: break;              \
+  }
+  if (dtype == CULLAVO_DT_F32) { GRD(float) }
+  else { GRD(u16) }
+#undef GRD
+#undef GR
   cullavo_set_error("attention: head_dim must be 16, 32, 64 or 128");
   return CULLAVO_EUNSUPPORTED;
 }

@@ -142,6 +142,10 @@ int cullavo_attn_generic_fwd(const void* q, int64_t ldq, const void* k, int64_t 
 int cullavo_attn_generic_fwd_cached(const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
                                     int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B, int H,
                                     int Lq, int past, int D, float scale, const int32_t* ks, int dtype, hipStream_t s);
+int cullavo_attn_generic_fwd_ragged(const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
+                                    int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B, int H,
+                                    int Lq, int cap, int D, float scale, const int32_t* ks, const int32_t* kv_len,
+                                    const int32_t* q_pad, int dtype, hipStream_t s);
 int cullavo_attn_generic_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                              const void* o, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
                              float* delta, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv,

@@ -33,6 +33,26 @@ __global__ __launch_bounds__(256) void kv_append_k(const u16* __restrict__ ks, i
   }
 }
 
+// kv_append_k for a left-padded [B, Lnew] block (cullavo_kv_append_ragged): row t of sequence b is
+// padding when t < q_pad[b] and is not written; the others land at start[b] + t - q_pad[b]
+__global__ __launch_bounds__(256) void kv_append_ragged_k(const u16* __restrict__ ks, int64_t ldks,
+                                                         const u16* __restrict__ vs, int64_t ldvs,
+                                                         u16* __restrict__ kc, u16* __restrict__ vc, int64_t ld_tok,
+                                                         int64_t ld_b, const int32_t* __restrict__ start,
+                                                         const int32_t* __restrict__ q_pad, int B, int Lnew,
+                                                         int64_t hd) {
+  const int64_t per_row = hd / 8, total = (int64_t)B * Lnew * per_row;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / per_row, c = (i % per_row) * 8;
+    const int b = (int)(row / Lnew), t = (int)(row % Lnew);
+    const int pad = max(q_pad[b], 0);
+    if (t < pad) continue;
+    const int64_t dst = (int64_t)b * ld_b + (int64_t)(start[b] + t - pad) * ld_tok + c;
+    *reinterpret_cast<u16x8*>(kc + dst) = *reinterpret_cast<const u16x8*>(ks + row * ldks + c);
+    *reinterpret_cast<u16x8*>(vc + dst) = *reinterpret_cast<const u16x8*>(vs + row * ldvs + c);
+  }
+}
+
 // ROPE (cullavo_attn_decode_rope): the step's RoPE + KV append fused in front (rope_append8_k's
 // arithmetic, elementwise.hip): every workgroup rotates its head's query row itself (q is read, not
 // rotated in place), the workgroup whose chunk holds the new row start[b] rotates that row's key,
@@ -268,6 +288,23 @@ extern "C" int cullavo_kv_append(const void* k, int64_t ldk, const void* v, int6
   kv_append_k<<<g, 256, 0, s>>>((const u16*)k, ldk, (const u16*)v, ldv, (u16*)k_cache, (u16*)v_cache, ld_tok,
                                 ld_batch, start, B, Lnew, hd);
   return cullavo_check_launch("kv_append");
+}
+
+extern "C" int cullavo_kv_append_ragged(const void* k, int64_t ldk, const void* v, int64_t ldv, void* k_cache,
+                                        void* v_cache, int64_t ld_tok, int64_t ld_batch, const int32_t* start,
+                                        const int32_t* q_pad, int B, int Lnew, int64_t hd, void* stream) {
+  CV_REQUIRE(hd % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ld_tok % 8 == 0 && ld_batch % 8 == 0, CULLAVO_EINVAL,
+             "kv_append_ragged: sizes and strides must be multiples of 8");
+  CV_REQUIRE(start != nullptr, CULLAVO_EINVAL, "kv_append_ragged: start positions");
+  CV_REQUIRE(q_pad != nullptr, CULLAVO_EINVAL, "kv_append_ragged: q_pad (the padding rows per sequence) is null");
+  CV_REQUIRE(B >= 0 && Lnew >= 0, CULLAVO_EINVAL, "kv_append_ragged: B and Lnew must not be negative");
+  if (B == 0 || Lnew == 0) return CULLAVO_OK;
+  hipStream_t s = CV_STREAM(stream);
+  const int64_t work = (int64_t)B * Lnew * (hd / 8);
+  const int g = (int)std::min<int64_t>(cdiv(work, 256), 8192);
+  kv_append_ragged_k<<<g, 256, 0, s>>>((const u16*)k, ldk, (const u16*)v, ldv, (u16*)k_cache, (u16*)v_cache, ld_tok,
+                                       ld_batch, start, q_pad, B, Lnew, hd);
+  return cullavo_check_launch("kv_append_ragged");
 }
 
 extern "C" size_t cullavo_attn_decode_workspace(int B, int H, int max_len, int D) {

@@ -15,7 +15,7 @@ several new tokens per sequence -- a follow-up turn, a second question about an 
 are already cached, the later pieces of a chunked prefill (generate(prefill_chunk=N)): RoPE at
 next_pos .. next_pos + n - 1, kv_append, then attn_fwd_cached, the causal flash kernel with a
 query offset over the cache's first length + n rows (reference: any number of new input_ids with
-past_key_values, arch_cullavo.py:605-647). Its new tokens must all be attended. Left-padded batches are
+past_key_values, arch_cullavo.py:605-647). New turns of unequal length: the ragged cache below. Left-padded batches are
 supported through kv_start (keys before the first attended token are masked); a prompt with
 holes in its attention mask is not (decode attention reads one contiguous key range).
 Sampling (temperature, top-k, top-p, multinomial; or greedy) follows HF's warper order on the
@@ -27,6 +27,19 @@ writes the next step's input token on the device, so a generation is a row of gr
 one host read of `finished` every 16 tokens. It takes 1 <= top_k <= 1024; top_k=0 (the nucleus
 over the full vocabulary), repetition penalties and beam search stay with the host loop or are
 not implemented.
+
+Ragged cache (batched follow-up turns of unequal length). KVCache.lengths (int32 [B], or None: every
+sequence holds `length` rows, everything above) makes the cache compact and ragged: sequence b owns
+rows [0, lengths[b]) with no holes and attends [kv_start[b], lengths[b]) -- the keys and RoPE
+positions HF computes from a holed attention mask and position_ids = cumsum(mask) - 1
+(arch_cullavo.py:605-636), without storing or streaming a masked key. A new turn arrives as a
+left-padded [B, Lnew] block with its mask; q_pad[b] is the row's count of leading zeros (a row of
+zeros: nothing new), the live rows get positions next_pos[b] .., kv_append_ragged writes them at
+lengths[b] .. and attn_fwd_ragged attends with kv_len = lengths + n_new. generate(compact_cache=True)
+keeps the cache ragged while it decodes: a row stops advancing with the step that would feed its
+eos (DecodeGraph(live=True): pos += live, start += live), so the pads a finished row is fed land on
+one scratch row behind its length and a second turn continues every conversation from exactly its
+own tokens. `length` stays the high-water mark max(lengths).
 """
 from __future__ import annotations
 
@@ -66,7 +79,8 @@ class KVCache:
         self.k = torch.empty((n_layers, B, max_len, H * D), dtype=dtype, device=device)
         self.v = torch.empty_like(self.k)
         self.B, self.max_len, self.H, self.D = B, max_len, H, D
-        self.length = 0                      # rows written (same for every sequence)
+        self.length = 0                      # rows written: every sequence's, or max(lengths) when ragged
+        self.lengths = None                  # int32 [B]: rows written per sequence (None: `length` for all)
         self.kv_start = None                 # int32 [B]: first attended key (left padding)
         self.next_pos = None                 # int64 [B]: RoPE position of the next token
 
@@ -86,8 +100,31 @@ class KVCache:
         """transformers' legacy tuple: ((key, value) [B, H, L, D] per layer), views of this cache"""
         return tuple(self[i] for i in range(len(self)))
 
+    def make_ragged(self):
+        """give the cache per-sequence lengths (all `length`); a ragged cache stays ragged"""
+        if self.lengths is None:
+            self.lengths = torch.full((self.B,), self.length, dtype=torch.int32, device=self.k.device)
+        return self
+
+    def key_mask(self):
+        """bool [B, length]: the cache slots sequence b attends, kv_start[b] <= j < lengths[b]"""
+        j = torch.arange(self.length, device=self.k.device)[None]
+        m = j < (self.lengths[:, None] if self.lengths is not None else self.length)
+        if self.kv_start is not None:
+            m = m & (j >= self.kv_start[:, None])
+        return m.expand(self.B, self.length)
+
+    def advance_ragged(self, n_new):
+        """the bookkeeping of a ragged step that appended n_new[b] (int [B]) rows to sequence b"""
+        self.make_ragged()
+        n_new = n_new.to(self.lengths.device)
+        self.lengths = self.lengths + n_new.to(torch.int32)
+        self.next_pos = self.next_pos + n_new.to(self.next_pos.dtype)
+        self.length = int(self.lengths.max())
+
     def grow(self, max_len: int):
-        """re-allocate with room for max_len rows per sequence, keeping the filled rows"""
+        """re-allocate with room for max_len rows per sequence, keeping the filled rows (a ragged
+        cache's rows up to its longest sequence's)"""
         if max_len <= self.max_len:
             return
         k = torch.empty((self.k.shape[0], self.B, max_len, self.k.shape[3]), dtype=self.k.dtype, device=self.k.device)
@@ -140,6 +177,23 @@ class KVCache:
         return cache
 
 
+def new_chunk_padding(attention_mask, Lnew: int):
+    """q_pad of a cached step's new chunk: the number of leading zeros of each row of the mask's last
+    Lnew columns (a [B, Lnew] mask of the new tokens or a [B, past + Lnew] one), int32 [B]; None when
+    every new token is attended. A row of zeros is allowed (q_pad = Lnew: nothing new for that
+    sequence); a zero after a row's first attended new token is refused."""
+    if attention_mask.dim() != 2 or attention_mask.shape[1] < Lnew:
+        raise ValueError(f"attention_mask {tuple(attention_mask.shape)}: expected [B, >= {Lnew}]")
+    new = attention_mask[:, -Lnew:] != 0
+    if not bool((~new).any()):
+        return None
+    lead = (new.to(torch.int64).cumsum(-1) == 0).sum(-1)
+    if bool((new.sum(-1) + lead != Lnew).any()):
+        raise NotImplementedError("a continuation chunk with masked tokens after a row's first attended one "
+                                  "(left padding only: the cache is compact, a hole has no row)")
+    return lead.to(torch.int32)
+
+
 def _nf4_linear(q, x, w, group, residual=None):
     """One Linear of the decode step: on the NF4 copy q = (codes, absmax) when the layer has one
     (the LoRA term materialised and passed as the epilogue addend; w goes along, so a shape on which
@@ -151,11 +205,14 @@ def _nf4_linear(q, x, w, group, residual=None):
 
 
 def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int, start, kv_len,
-                attn_len: int | None = None):
+                attn_len: int | None = None, q_pad=None):
     """One LlamaDecoderLayer over Lnew new rows per sequence (prefill: Lnew = prompt length on an
     empty cache; decode: Lnew = 1; continuation: Lnew > 1 on a filled cache, attending the cached
     prefix through ops.attn_fwd_cached), appending their keys/values to the cache. No autograd.
-    attn_len: the key range decode attention is sized for (default: the filled rows + 1)."""
+    attn_len: the key range decode attention is sized for (default: the filled rows + 1).
+    q_pad (int32 [B]): the ragged step -- the rows are a left-padded [B, Lnew] block, sequence b's live
+    rows go to cache rows start[b] .. (ops.kv_append_ragged) and attend with kv_len[b] = start[b] +
+    Lnew - q_pad[b] (ops.attn_fwd_ragged)."""
     cfg = layer.cfg
     d, H, D = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim
     lg = layer.lora_groups
@@ -182,7 +239,12 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int,
         x1, _ = ops.rmsnorm_fwd(h, layer.input_layernorm.weight, cfg.rms_norm_eps)
         qkv = _nf4_linear(nf4.get("qkv"), x1, layer.w_qkv(), lg["qkv"])
     q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-    if Lnew == 1 and qkv.dtype == torch.bfloat16 and FUSE_DECODE_ROPE:
+    if q_pad is not None:
+        ops.rope(q, k, sctx.position_ids, hq=H, hk=H, head_dim=D, theta=cfg.rope_theta)
+        ops.kv_append_ragged(k, v, cache.k[li], cache.v[li], start, q_pad, B=B, Lnew=Lnew)
+        o, _ = ops.attn_fwd_ragged(q, cache.k[li], cache.v[li], kv_len, B=B, H=H, Lq=Lnew, D=D, scale=D ** -0.5,
+                                   q_pad=q_pad, kv_start=sctx.kv_start)
+    elif Lnew == 1 and qkv.dtype == torch.bfloat16 and FUSE_DECODE_ROPE:
         # decode: RoPE, the cache append and attention in one pass (the cache row is start[b])
         o = ops.attn_decode_rope(q, k, v, sctx.position_ids, cache.k[li], cache.v[li], start, B=B, H=H, D=D,
                                  max_len=attn_len if attn_len is not None else cache.length + 1,
@@ -194,7 +256,9 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int,
     else:
         ops.rope(q, k, sctx.position_ids, hq=H, hk=H, head_dim=D, theta=cfg.rope_theta)
         ops.kv_append(k, v, cache.k[li], cache.v[li], start, B=B, Lnew=Lnew)
-    if Lnew > 1 and cache.length > 0:
+    if q_pad is not None:
+        pass
+    elif Lnew > 1 and cache.length > 0:
         # continuation: the new rows against the cached prefix and themselves (their keys / values
         # were appended just above), causal from the row's own position
         o, _ = ops.attn_fwd_cached(q, cache.k[li], cache.v[li], B=B, H=H, Lq=Lnew, past=cache.length, D=D,
@@ -311,9 +375,15 @@ class DecodeGraph:
     sizes it for prompt + max_new_tokens).
     With a sampler (SamplerState) the captured step ends with the sampling kernel on its logits and
     reads its token from the sampler's next_ids, which that kernel wrote one replay earlier:
-    advance() replays with no host-to-device token copy. Without one the graph is what it was."""
+    advance() replays with no host-to-device token copy. Without one the graph is what it was.
+    On a ragged cache `start` begins at cache.lengths (the per-row start[b] is what the decode kernels
+    take) and becomes cache.lengths, as `pos` becomes cache.next_pos. live=True adds a [B] int32 buffer
+    `live`: the captured step ends with pos += live, start += live instead of += 1, so a row whose
+    live[b] is 0 appends nothing (its key / value land on the scratch row start[b], which the next
+    live step overwrites). With a sampler the step sets live = ~finished itself, before it samples;
+    without one the caller writes `live` before each step()."""
 
-    def __init__(self, model, cache: KVCache, sampler: SamplerState | None = None):
+    def __init__(self, model, cache: KVCache, sampler: SamplerState | None = None, live: bool = False):
         lm = model.language_model
         self.cache, self.lm = cache, lm
         B = cache.B
@@ -321,7 +391,11 @@ class DecodeGraph:
         self.sampler = sampler
         self.ids = sampler.next_ids if sampler is not None else torch.zeros(B, dtype=torch.long, device=dev)
         self.pos = cache.next_pos.to(torch.int64).clone()
-        self.start = torch.full((B,), cache.length, dtype=torch.int32, device=dev)
+        if cache.lengths is not None:
+            self.start = cache.lengths.to(torch.int32).clone()
+        else:
+            self.start = torch.full((B,), cache.length, dtype=torch.int32, device=dev)
+        self.live = torch.ones(B, dtype=torch.int32, device=dev) if live else None
         self.embed = model.get_input_embeddings()
         # the captured kernels hold raw pointers into the layers' NF4 copies: keep the tensors alive
         # for the graph's lifetime even if quant.nf4_weights() drops them from the layers meanwhile
@@ -341,11 +415,17 @@ class DecodeGraph:
             ops._TRACE["key"] = traced
         torch.cuda.current_stream(dev).wait_stream(stream)
         cache.next_pos = self.pos  # advanced in place by every replay
+        if cache.lengths is not None:
+            cache.lengths = self.start  # likewise (cache.length: the high-water mark, by step / advance)
 
     def _step(self):
         lm, cache = self.lm, self.cache
         cfg = lm.cfg
         B = cache.B
+        if self.live is not None and self.sampler is not None:
+            # a row advances until the step that would feed its eos: `finished` as the sampling kernel
+            # left it one replay earlier, read before this step's sampling changes it
+            self.live.copy_(self.sampler.finished == 0)
         h = self.embed(self.ids[:, None]).reshape(B, cfg.hidden_size)
         sctx = StepContext(B, 1, self.pos[:, None], cache.kv_start, lora_seed=0)
         # the unfused decode attention reads kv_len = start + 1 (the fused one derives it from start)
@@ -356,8 +436,12 @@ class DecodeGraph:
         logits = ops.linear(x, lm.lm_head.weight)
         if self.sampler is not None:  # the next step's token, written where this graph's embedding reads it
             self.sampler.sample(logits)
-        self.pos.add_(1)
-        self.start.add_(1)
+        if self.live is not None:
+            self.pos.add_(self.live)
+            self.start.add_(self.live)
+        else:
+            self.pos.add_(1)
+            self.start.add_(1)
         return logits.view(B, 1, -1)
 
     def advance(self):
@@ -402,6 +486,50 @@ def _infer_rows(lm, embeds, position_ids, cache: KVCache):
     return logits.view(B, Lnew, -1)
 
 
+def _infer_ragged(lm, embeds, q_pad, position_ids, cache: KVCache, prefill_chunk: int | None):
+    """lm_infer's ragged branch: embeds [B, Lnew, d] is a left-padded block whose first q_pad[b] rows
+    of sequence b are padding (q_pad None: none), appended to a cache that is, or hereby becomes,
+    ragged. Returns logits [B, Lnew, V]; the padding rows' logits mean nothing."""
+    B, Lnew, d = embeds.shape
+    cfg = lm.cfg
+    dev = embeds.device
+    cache.make_ragged()
+    q_pad = (torch.zeros(B, dtype=torch.int32, device=dev) if q_pad is None
+             else q_pad.to(device=dev, dtype=torch.int32))
+    # one token per sequence runs the decode kernels at start = lengths, as the decode graph does:
+    # a padding row's key / value land on the scratch row behind its length and it does not advance
+    decode = Lnew == 1
+    need = cache.length + 1 if decode else int((cache.lengths + (Lnew - q_pad)).max())
+    if need > cache.max_len:  # in 256-row steps, as the decode steps grow it
+        cache.grow(cache.max_len + 256 * -(-(need - cache.max_len) // 256))
+    if position_ids is None:
+        # position next_pos[b] + i - q_pad[b] on the live rows, any finite value on the padding
+        position_ids = (cache.next_pos[:, None] + torch.arange(Lnew, device=dev) - q_pad[:, None]).clamp_(min=0)
+    if decode:
+        position_ids = torch.where(q_pad[:, None] > 0, cache.next_pos[:, None], position_ids)
+    step = Lnew if prefill_chunk is None else prefill_chunk
+    if step < 1:
+        raise ValueError(f"prefill_chunk must be positive, got {prefill_chunk}")
+    logits = []
+    for c in range(0, Lnew, step):
+        # a piece is columns c .. c + w of the block, its padding the part of q_pad inside it
+        w = min(step, Lnew - c)
+        qp = (q_pad - c).clamp_(0, w)
+        sctx = StepContext(B, w, position_ids[:, c:c + w], cache.kv_start, lora_seed=0)
+        h = embeds[:, c:c + w].reshape(B * w, d).contiguous()
+        start = cache.lengths
+        kv_len = start + (w - qp)
+        for li, layer in enumerate(lm.model.layers):
+            if decode:
+                h = layer_infer(layer, h, sctx, cache, li, 1, start, start + 1, attn_len=cache.length + 1)
+            else:
+                h = layer_infer(layer, h, sctx, cache, li, w, start, kv_len, q_pad=qp)
+        cache.advance_ragged(w - qp)
+        x, _ = ops.rmsnorm_fwd(h, lm.model.norm.weight, cfg.rms_norm_eps)
+        logits.append(ops.linear(x, lm.lm_head.weight).view(B, w, -1))
+    return logits[0] if len(logits) == 1 else torch.cat(logits, 1)
+
+
 def lm_infer(lm, embeds, attention_mask, position_ids, cache: KVCache | None, max_len: int,
              prefill_chunk: int | None = None):
     """LlamaForCausalLM with a KV cache: prefill (cache None or empty), one decode step, or a
@@ -431,6 +559,10 @@ def lm_infer(lm, embeds, attention_mask, position_ids, cache: KVCache | None, ma
         if position_ids is None:
             position_ids = (am.cumsum(-1) - 1).masked_fill(am == 0, 1)
         cache.next_pos = position_ids[:, -1].to(torch.int64) + 1
+    elif cache.lengths is not None:
+        # a ragged cache: any chunk (one token per sequence included) takes the ragged kernels
+        q_pad = new_chunk_padding(attention_mask, Lnew) if attention_mask is not None else None
+        return _infer_ragged(lm, embeds, q_pad, position_ids, cache, prefill_chunk), cache
     elif Lnew == 1:
         if cache.length + 1 > cache.max_len:  # room for 256 more steps (one copy per 256 steps)
             cache.grow(cache.max_len + 256)
@@ -440,13 +572,11 @@ def lm_infer(lm, embeds, attention_mask, position_ids, cache: KVCache | None, ma
     else:
         if attention_mask is not None:
             # a 2-D mask ending in the new tokens (past + new rows, or the new ones alone): the cached
-            # part is the cache's own state (kv_start); the new tokens must all be attended (the
-            # kernels read one contiguous key range)
-            if attention_mask.dim() != 2 or attention_mask.shape[1] < Lnew:
-                raise ValueError(f"attention_mask {tuple(attention_mask.shape)}: expected [B, >= {Lnew}]")
-            if bool((attention_mask[:, -Lnew:] == 0).any()):
-                raise NotImplementedError("a continuation chunk with masked tokens (every new token of a cached "
-                                          "step must be attended)")
+            # part is the cache's own state (kv_start). Zeros in the new part may only lead a row (a
+            # left-padded turn, which makes the cache ragged); all ones is the uniform step below
+            q_pad = new_chunk_padding(attention_mask, Lnew)
+            if q_pad is not None:
+                return _infer_ragged(lm, embeds, q_pad, position_ids, cache, prefill_chunk), cache
         if cache.length + Lnew > cache.max_len:  # in 256-row steps, as the decode steps grow it
             cache.grow(cache.max_len + 256 * -(-(cache.length + Lnew - cache.max_len) // 256))
         if position_ids is None:

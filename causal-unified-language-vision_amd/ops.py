@@ -22,6 +22,7 @@ __all__ = [
     "act_bwd", "colsum", "rope", "attn_fwd", "attn_fwd_cached", "attn_bwd", "embedding_fwd", "embedding_bwd",
     "im2col_patches", "vision_embed_ln", "merge_plan", "row_gather2", "shift_targets", "ce_fwd",
     "ce_reduce", "ce_bwd", "adamw", "sumsq", "clip_coef", "scale_inplace", "kv_append", "attn_decode",
+    "kv_append_ragged", "attn_fwd_ragged",
     "clip_image_preprocess", "visimage_geometry", "draw_boxes",
     "nf4_quantize", "nf4_dequantize", "nf4_decode_linear", "sample_token",
 ]
@@ -599,6 +600,26 @@ def kv_append(k, v, k_cache, v_cache, start, *, B: int, Lnew: int):
          k_cache.stride(0), _ptr(start), B, Lnew, hd, _stream())
 
 
+def _int32_rows(name: str, t, B: int):
+    """an int32 [B] contiguous device tensor (the per-sequence values of the ragged entry points)"""
+    if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != B or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous int32 [{B}] tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def kv_append_ragged(k, v, k_cache, v_cache, start, q_pad, *, B: int, Lnew: int):
+    """cullavo_kv_append_ragged: kv_append of a left-padded [B, Lnew] block. Row t >= q_pad[b] of
+    sequence b goes to cache row start[b] + t - q_pad[b]; the q_pad[b] padding rows are not written.
+    start, q_pad int32 [B]; q_pad all zero writes what kv_append writes."""
+    _dev(k, v, k_cache, v_cache, start, q_pad)
+    _int32_rows("start", start, B)
+    _int32_rows("q_pad", q_pad, B)
+    if k_cache.dim() != 3 or k_cache.stride(2) != 1 or v_cache.stride() != k_cache.stride():
+        raise ValueError("expected caches [B, Lmax, H*D] with unit column stride and the same strides")
+    hd = k_cache.shape[-1]
+    call("kv_append_ragged", _ptr(k), _ld(k), _ptr(v), _ld(v), _ptr(k_cache), _ptr(v_cache), k_cache.stride(1),
+         k_cache.stride(0), _ptr(start), _ptr(q_pad), B, Lnew, hd, _stream())
+
+
 def attn_decode_rope(q, k, v, position_ids, k_cache, v_cache, start, *, B: int, H: int, D: int, max_len: int,
                      scale: float, theta: float, kv_start=None, out=None):
     """cullavo_attn_decode_rope: rope_kv_append (Lnew = 1) + attn_decode over keys
@@ -638,6 +659,34 @@ def attn_fwd_cached(q, k_cache, v_cache, *, B: int, H: int, Lq: int, past: int, 
     lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
     call("attn_fwd_cached", _ptr(q), _ld(q), _ptr(k_cache), _ptr(v_cache), k_cache.stride(1), k_cache.stride(0),
          _ptr(o), _ld(o), _ptr(lse), B, H, Lq, past, D, float(scale), _ptr(kv_start), _dt(q), _stream())
+    return o, lse
+
+
+def attn_fwd_ragged(q, k_cache, v_cache, kv_len, *, B: int, H: int, Lq: int, D: int, scale: float, q_pad=None,
+                    kv_start=None, out=None):
+    """cullavo_attn_fwd_ragged: attn_fwd_cached with a prefix length per sequence. q [B*Lq, >=H*D] is
+    a left-padded [B, Lq] block whose first q_pad[b] rows of sequence b are padding (q_pad None: no
+    padding); kv_len[b] counts the filled rows of b's cache, this call's Lq - q_pad[b] new rows
+    included. Query i >= q_pad[b] sits at cache row kv_len[b] - Lq + i and attends keys
+    kv_start[b] <= j <= that row; padding queries return a zero row and lse = +inf. kv_len, q_pad,
+    kv_start: int32 [B]. Returns (o [B*Lq, H*D], lse [B, H, Lq] f32)."""
+    _dev(q, k_cache, v_cache, kv_len, q_pad, kv_start)
+    if k_cache.dim() != 3 or k_cache.stride(2) != 1 or v_cache.stride() != k_cache.stride():
+        raise ValueError("expected caches [B, Lmax, H*D] with unit column stride and the same strides")
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise TypeError(f"q {q.dtype} and the caches {k_cache.dtype} / {v_cache.dtype} must share a dtype")
+    if q.shape[0] != B * Lq or k_cache.shape[0] != B:
+        raise ValueError(f"q {tuple(q.shape)} / caches {tuple(k_cache.shape)} vs B {B}, Lq {Lq}")
+    _int32_rows("kv_len", kv_len, B)
+    if q_pad is not None:
+        _int32_rows("q_pad", q_pad, B)
+    if kv_start is not None:
+        _int32_rows("kv_start", kv_start, B)
+    o = out if out is not None else torch.empty((B * Lq, H * D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+    call("attn_fwd_ragged", _ptr(q), _ld(q), _ptr(k_cache), _ptr(v_cache), k_cache.stride(1), k_cache.stride(0),
+         _ptr(o), _ld(o), _ptr(lse), B, H, Lq, _ptr(kv_len), _ptr(q_pad), D, float(scale), _ptr(kv_start), _dt(q),
+         _stream())
     return o, lse
 
 

@@ -61,7 +61,8 @@ extern "C" {
    cullavo_gemm_set_tile_rate, every value of cullavo_gemm_set_epilogue but 0 and 1, and the second
    mode of cullavo_gemm_set_msplit). cullavo_sample_token
    was added under 8 without a bump, as cullavo_lora_dx was under its version: a pure addition that
-   changes no existing signature. A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
+   changes no existing signature; so were cullavo_attn_fwd_ragged and cullavo_kv_append_ragged under 9
+   (the ragged KV cache: two new entry points, nothing existing touched). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
 #define CULLAVO_ABI_VERSION 9
 
 int cullavo_abi_version(void);
@@ -390,6 +391,35 @@ int cullavo_attn_fwd_cached(const void* q, int64_t ldq, const void* k_cache, con
                             int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B,
                             int H, int Lq, int past, int D, float scale, const int32_t* kv_start,
                             int dtype, void* stream);
+/* The ragged KV cache (added under ABI 9, additive): a batch whose sequences have caches of unequal
+ * length and whose new turns are of unequal length, packed as a left-padded [B, Lq] block -- HF's
+ * generation batch, whose padded slots the reference masks and skips in position_ids = cumsum(mask)
+ * - 1 (cullavo/arch_cullavo.py:605-636). Here the cache is compact: sequence b owns cache rows
+ * [0, kv_len[b]) with no holes, so no masked key is stored or streamed.
+ * cullavo_kv_append_ragged is cullavo_kv_append with q_pad [B]: row t of sequence b is padding when
+ * t < q_pad[b] and is not written at all; the others go to cache row start[b] + t - q_pad[b]
+ * (cullavo_kv_append would write the padding over the q_pad[b] valid rows below). q_pad all zero
+ * writes exactly what cullavo_kv_append writes. */
+int cullavo_kv_append_ragged(const void* k, int64_t ldk, const void* v, int64_t ldv, void* k_cache, void* v_cache,
+                             int64_t ld_tok, int64_t ld_batch, const int32_t* start, const int32_t* q_pad, int B,
+                             int Lnew, int64_t hd, void* stream);
+/* cullavo_attn_fwd_ragged is cullavo_attn_fwd_cached with `int past` replaced by kv_len [B] (the
+ * filled rows of sequence b's cache INCLUDING this call's new rows) and q_pad [B] (nullable: 0; the
+ * leading padding rows of sequence b inside the [B, Lq] query block). With n_new[b] = Lq - q_pad[b],
+ * query i >= q_pad[b] sits at cache row kv_len[b] - Lq + i and attends keys kv_start[b] <= j <=
+ * kv_len[b] - Lq + i; queries i < q_pad[b] return a zero row and lse = +inf, as any query with no
+ * visible key. kv_len[b] - Lq may be negative (a short cache behind a long pad); n_new[b] = 0 is
+ * legal (all of b's rows are zero). Sequence b's LDS-DMA descriptors end at row kv_len[b], a query
+ * tile wholly inside the padding fetches nothing. With q_pad = 0 and kv_len[b] = past + Lq for all b
+ * the result is cullavo_attn_fwd_cached's bit for bit. Errors (CULLAVO_EINVAL, before any launch):
+ * kv_len null, Lq < 1, ld_batch < ld_tok, and the stride / head-dim / dtype errors of
+ * cullavo_attn_fwd_cached. The values kv_len and q_pad point to are on the device and cannot be
+ * validated: the kernel clamps kv_len[b] to [0, ld_batch / ld_tok] and q_pad[b] to [0, Lq], so a
+ * bad value changes the result but never fetches outside the sequence's slab of the cache. */
+int cullavo_attn_fwd_ragged(const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
+                            int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B,
+                            int H, int Lq, const int32_t* kv_len, const int32_t* q_pad, int D, float scale,
+                            const int32_t* kv_start, int dtype, void* stream);
 /* Decode-step Linear over M <= 16 rows (one token per sequence; reference: the cached forward's
  * decoder layer, cullavo/arch_cullavo.py:605-636) with its input transform fused into the weight
  * stream (csrc/gemv.hip): y[M,N] = X W^T (+ residual), W [N,K] bf16 (ldw), where X is
