@@ -31,7 +31,10 @@
   for (int k0 = 0; k0 < kend; k0 += KB) {
     __syncthreads();
     stage_rows<T>(sK, LD, Kb, ldk, krow0 + k0, min(KB, Lk - k0), KB, D);
-    stage_rows<T>(sV, LD, Vb, ldvt, krow0 + k0, min(KB, Lk - k0), KB, D);
+    if (CACHED)  // the cache rows below kv_start may hold anything (attn_generic.hip, stage_rows_from)
+      stage_rows_from<T>(sV, LD, Vb, ldvt, krow0 + k0, ks - k0, min(KB, Lk - k0), KB, D);
+    else
+      stage_rows<T>(sV, LD, Vb, ldvt, krow0 + k0, min(KB, Lk - k0), KB, D);
     __syncthreads();
     float s[KB / 4];
     float bmax = -INFINITY;

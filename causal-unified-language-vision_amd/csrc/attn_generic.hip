@@ -26,6 +26,18 @@ DEV void stage_rows(float* dst, int ld_dst, const T* src, int64_t ld_src, int64_
   }
 }
 
+// stage_rows with zeros in place of rows r < r_lo as well: the V rows of cache keys below kv_start.
+// Their probability is 0, but the output takes fmaf(0, v, o), which a non-finite v turns into NaN;
+// for a finite cache fmaf(0, v, o) and fmaf(0, 0, o) are the same value.
+template <typename T>
+DEV void stage_rows_from(float* dst, int ld_dst, const T* src, int64_t ld_src, int64_t row0, int r_lo,
+                         int nrows_valid, int nrows, int D) {
+  for (int idx = threadIdx.x; idx < nrows * D; idx += 256) {
+    const int r = idx / D, c = idx - r * D;
+    dst[r * ld_dst + c] = (r >= r_lo && r < nrows_valid) ? Elt<T>::ld(src, (row0 + r) * ld_src + c) : 0.f;
+  }
+}
+
 DEV bool visible(int64_t qg, int64_t jg, int Lk, int ks, bool causal) {
   return jg < Lk && jg >= ks && (!causal || jg <= qg);
 }
@@ -35,7 +47,9 @@ DEV bool visible(int64_t qg, int64_t jg, int Lk, int ks, bool causal) {
 // CACHED (cullavo_attn_fwd_cached; causal): the Lq queries are the last Lq positions of Lk = past +
 // Lq keys (query i sees keys <= past + i), K / V are one layer's KV cache, both with token stride
 // ldk, sequence b at element offset b * ldv (ldv carries the cache's batch stride); rows >= Lk of
-// the cache are never staged. lse may then be null.
+// the cache are never staged, and V rows below kv_start[b] are staged as zeros (stage_rows_from): the
+// output is finite whatever those rows hold. lse may then be null. The packed kernel (CACHED false)
+// stages every row below Lk: its K / V must be finite below kv_start too.
 // RAGGED (cullavo_attn_fwd_ragged; CACHED, causal): Lk is sequence b's own kv_len[b] and the first
 // qpad = q_pad[b] queries of its left-padded block are padding -- they see no key (a zero row, lse =
 // +inf), and a query block wholly inside the padding stages no key block. Lk - Lq may be negative.

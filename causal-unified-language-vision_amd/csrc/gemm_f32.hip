@@ -3,7 +3,10 @@
 // built on f32 arenas computes the reference's fp32 module chain (tf:llama/modeling_llama.py,
 // tf:clip/modeling_clip.py, tf:llava/modeling_llava.py in fp32) with one f32 rounding per
 // product: v_mfma_f32_16x16x4_f32 is an exact k-ordered f32 fma chain
-// (cdna_hip_programming.md "FP32-input MFMA").
+// (cdna_hip_programming.md "FP32-input MFMA"): held bitwise against an exact emulation of that chain by
+// tests/test_parity_accuracy_gpu.py (0 differing elements on the MI355X, zero-padded K tails included).
+// The shared argument checks of gemm_impl apply here too (N, lda, ldb, ldc, ldr % 8, K % 8 unless both
+// layouts are 1, M % 8 for a_layout 1), so the per-element guards of f32_load never split a group of 4.
 //
 // 128x128 tile, 4 waves (2x2, 64x64 each = 4x4 MFMA tiles), BK = 16, operands staged through
 // registers into k-major LDS images (both layouts; layout 0 is transposed on the LDS write),
