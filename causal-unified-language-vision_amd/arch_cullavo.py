@@ -331,7 +331,7 @@ class CuLLaVOModel(nn.Module):
         input_ids=<the left-padded new turns>, attention_mask=<[B, S] or [B, past + S]>) then
         continues every conversation; a ragged input cache or a left-padded new turn takes the
         ragged path without the flag."""
-        from .generation import KVCache, device_sampling, sample_next
+        from .generation import DecodeStepper, HostSampler, KVCache, SamplerState, device_sampling
         if not use_cache:
             raise NotImplementedError("generate() runs on the KV cache (use_cache=True)")
         on_device = device_sampling(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
@@ -367,42 +367,26 @@ class CuLLaVOModel(nn.Module):
         compact = bool(compact_cache) or cache.lengths is not None
         if compact:
             cache.make_ragged()
-        elif return_dict_in_generate:  # the cache's state before the first sampled token
-            len0, pos0 = cache.length, cache.next_pos.clone()
-        logits = out.logits[:, -1]
-        if on_device:
-            gen = self._generate_on_device(cache, logits, max_new_tokens, do_sample, temperature, top_k, top_p, seed,
-                                           eos_token_id, pad, kw, compact)
+        mark = cache.mark() if return_dict_in_generate and not compact else None
+        if on_device:  # the sampling kernel: in the decode graph's capture, or after each eager step
+            sampler = SamplerState(B, max_new_tokens, input_ids.device, do_sample=do_sample, temperature=temperature,
+                                   top_k=top_k, top_p=top_p, seed=seed if seed is not None else 0,
+                                   eos_token_id=eos_token_id, pad_token_id=pad, row_offset=kw.get("sample_offsets"))
         else:
-            finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
-            new = []
-            # the decode steps replay one captured HIP graph (generation.DecodeGraph) unless asked not to
-            graph = None
-            if kw.get("decode_graph", True) and max_new_tokens > 1 and input_ids.is_cuda:
-                from .generation import DecodeGraph
-                graph = DecodeGraph(self, cache, live=compact)
-            check_every = 16  # all-finished test every 16 tokens: one host sync per 16 steps, not per step
-            for step in range(max_new_tokens):
-                tok = sample_next(logits, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
-                                  generator=generator)
-                tok = torch.where(finished, torch.full_like(tok, pad), tok)
-                new.append(tok)
-                if eos_token_id is not None:
-                    finished |= tok == eos_token_id
-                    if (step + 1) % check_every == 0 and bool(finished.all()):
-                        break
-                if step + 1 == max_new_tokens:
-                    break
-                if graph is not None:
-                    if compact:  # a finished row (its eos included) is fed but does not advance
-                        graph.live.copy_(~finished)
-                    logits = graph.step(tok)[:, -1]
-                else:
-                    live = (~finished)[:, None].to(torch.long) if compact else None
-                    out = self._forward_cached(tok[:, None], None, live, None, cache, None, cfg.vision_feature_layer,
-                                               cfg.vision_feature_select_strategy, None, True)
-                    logits = out.logits[:, -1]
-            gen = torch.stack(new, 1)
+            sampler = HostSampler(B, input_ids.device, eos_token_id=eos_token_id, pad_token_id=pad, do_sample=do_sample,
+                                  temperature=temperature, top_k=top_k, top_p=top_p, generator=generator)
+        sampler.sample(out.logits[:, -1])  # the first token, from the prefill logits
+        # the decode steps replay one captured HIP graph (generation.DecodeGraph) unless asked not to
+        stepper = DecodeStepper(self, cache, sampler, compact=compact,
+                                graph=kw.get("decode_graph", True) and max_new_tokens > 1 and input_ids.is_cuda)
+        check_every = 16  # all-finished test every 16 tokens: one host sync per 16 steps, not per step
+        n = 1
+        while n < max_new_tokens:
+            if eos_token_id is not None and n % check_every == 0 and bool(sampler.finished.all()):
+                break
+            stepper.feed(sampler)
+            n += 1
+        gen = sampler.tokens(n)
         if eos_token_id is not None:
             # HF stops at the first step where every row has finished; the steps run past it (at
             # most check_every - 1) hold only padding and are dropped
@@ -411,49 +395,10 @@ class CuLLaVOModel(nn.Module):
             if bool(all_done.any()):
                 gen = gen[:, :int(all_done.to(torch.int64).argmax()) + 1]
         sequences = torch.cat([input_ids, gen.to(input_ids.dtype)], 1)
-        if return_dict_in_generate and compact:
-            # per row, every real token but the row's last one is cached: no row advanced on a pad (the
-            # lengths and positions leave the decode graph's buffers)
-            cache.lengths, cache.next_pos = cache.lengths.clone(), cache.next_pos.clone()
-            cache.length = int(cache.lengths.max())
-            return CullavoGenerateOutput(sequences=sequences, past_key_values=cache)
-        if return_dict_in_generate:
-            # every returned token but the last is cached (rows a stopped batch ran past are dropped;
-            # the positions leave the decode graph's buffer)
-            fed = gen.shape[1] - 1
-            cache.length, cache.next_pos = len0 + fed, pos0 + fed
-            return CullavoGenerateOutput(sequences=sequences, past_key_values=cache)
-        return sequences
-
-    def _generate_on_device(self, cache, logits, max_new_tokens: int, do_sample: bool, temperature, top_k, top_p,
-                            seed, eos_token_id, pad, kw, compact: bool = False):
-        """generate()'s device loop: the first token by the sampling kernel on the prefill logits,
-        every later one by a replay of the decode graph that ends with that kernel; the host reads
-        `finished` every 16 replays and the tokens once at the end. Returns the new ids [B, n]."""
-        from .generation import DecodeGraph, SamplerState
-        cfg = self.config
-        B = logits.shape[0]
-        state = SamplerState(B, max_new_tokens, logits.device, do_sample=do_sample, temperature=temperature,
-                             top_k=top_k, top_p=top_p, seed=seed if seed is not None else 0,
-                             eos_token_id=eos_token_id, pad_token_id=pad, row_offset=kw.get("sample_offsets"))
-        state.sample(logits)
-        graph = None
-        if kw.get("decode_graph", True) and max_new_tokens > 1:
-            graph = DecodeGraph(self, cache, sampler=state, live=compact)
-        check_every = 16  # as the host loop: one host sync per 16 tokens
-        n = 1
-        while n < max_new_tokens:
-            if eos_token_id is not None and n % check_every == 0 and bool(state.finished.all()):
-                break
-            if graph is not None:
-                graph.advance()
-            else:
-                live = (state.finished == 0)[:, None].to(torch.long) if compact else None
-                out = self._forward_cached(state.next_ids[:, None], None, live, None, cache, None,
-                                           cfg.vision_feature_layer, cfg.vision_feature_select_strategy, None, True)
-                state.sample(out.logits[:, -1])
-            n += 1
-        return state.out_tokens[:, :n].clone()
+        if not return_dict_in_generate:
+            return sequences
+        cache.release(mark, fed=gen.shape[1] - 1)
+        return CullavoGenerateOutput(sequences=sequences, past_key_values=cache)
 
     # -- pieces ---------------------------------------------------------------------------------
     def _image_features(self, pixel_values, layer: int, strategy: str):

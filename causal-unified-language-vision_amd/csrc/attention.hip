@@ -1441,19 +1441,39 @@ extern "C" int cullavo_attn_set_bwd_tiles(int mode) {
   return prev;
 }
 
+// The argument checks the attention entry points share, each stated once. Macros, not functions:
+// CV_REQUIRE names the entry point it expands in (__func__) and returns from it. They read the entry
+// point's own dtype, D, H, Lq, Lk, causal, ldq, ld_tok, ld_batch and ldo.
+template <typename... S>
+static bool all_x8(S... ld) { return ((ld % 8 == 0) && ...); }
+template <typename... S>
+static bool all_hold(int64_t row, S... ld) { return ((ld >= row) && ...); }
+#define ATTN_REQUIRE_TYPE_AND_DIM()                                                                                \
+  CV_REQUIRE(dtype == CULLAVO_DT_BF16 || dtype == CULLAVO_DT_F32, CULLAVO_EUNSUPPORTED, "attention: bf16 / f32"); \
+  CV_REQUIRE(D == 16 || D == 32 || D == 64 || D == 128, CULLAVO_EUNSUPPORTED, "head_dim must be 16, 32, 64 or 128")
+#define ATTN_REQUIRE_CAUSAL_SQUARE() CV_REQUIRE(!causal || Lq == Lk, CULLAVO_EINVAL, "causal attention needs Lq == Lk")
+#define ATTN_REQUIRE_STRIDES_X8(...) \
+  CV_REQUIRE(all_x8(__VA_ARGS__), CULLAVO_EINVAL, "token strides must be multiples of 8")
+#define ATTN_REQUIRE_STRIDES_HOLD_HD(...) \
+  CV_REQUIRE(all_hold((int64_t)H * D, __VA_ARGS__), CULLAVO_EINVAL, "token stride smaller than H*D")
+#define ATTN_REQUIRE_CACHE_STRIDES()         \
+  ATTN_REQUIRE_STRIDES_X8(ldq, ld_tok, ldo); \
+  ATTN_REQUIRE_STRIDES_HOLD_HD(ldq, ld_tok, ldo); \
+  CV_REQUIRE(ld_batch % 8 == 0, CULLAVO_EINVAL, "the cache's batch stride must be a multiple of 8")
+// f32 storage (the parity mode) and the config-1 head dims run the kernels of attn_generic.hip
+#define ATTN_GENERIC (dtype == CULLAVO_DT_F32 || D < 64)
+
 extern "C" int cullavo_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
                                 int64_t ldv, void* o, int64_t ldo, float* lse, int B, int H, int Lq, int Lk,
                                 int D, float scale, int causal, const int32_t* kv_start, int dtype,
                                 void* stream) {
-  CV_REQUIRE(dtype == CULLAVO_DT_BF16 || dtype == CULLAVO_DT_F32, CULLAVO_EUNSUPPORTED, "attention: bf16 / f32");
-  CV_REQUIRE(D == 16 || D == 32 || D == 64 || D == 128, CULLAVO_EUNSUPPORTED, "head_dim must be 16, 32, 64 or 128");
-  CV_REQUIRE(!causal || Lq == Lk, CULLAVO_EINVAL, "causal attention needs Lq == Lk");
-  CV_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0, CULLAVO_EINVAL, "token strides must be multiples of 8");
-  CV_REQUIRE(ldq >= (int64_t)H * D && ldk >= (int64_t)H * D && ldv >= (int64_t)H * D && ldo >= (int64_t)H * D,
-             CULLAVO_EINVAL, "token stride smaller than H*D");
+  ATTN_REQUIRE_TYPE_AND_DIM();
+  ATTN_REQUIRE_CAUSAL_SQUARE();
+  ATTN_REQUIRE_STRIDES_X8(ldq, ldk, ldv, ldo);
+  ATTN_REQUIRE_STRIDES_HOLD_HD(ldq, ldk, ldv, ldo);
   if (B == 0 || H == 0 || Lq == 0) return CULLAVO_OK;
   hipStream_t s = CV_STREAM(stream);
-  if (dtype == CULLAVO_DT_F32 || D < 64)  // f32 parity mode / config-1 head dims: attn_generic.hip
+  if (ATTN_GENERIC)
     return cullavo_attn_generic_fwd(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, Lq, Lk, D, scale, causal, kv_start,
                                     dtype, s);
   const u16 *Q = (const u16*)q, *K = (const u16*)k, *V = (const u16*)v;
@@ -1469,20 +1489,16 @@ extern "C" int cullavo_attn_fwd_cached(const void* q, int64_t ldq, const void* k
                                        int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B,
                                        int H, int Lq, int past, int D, float scale, const int32_t* kv_start,
                                        int dtype, void* stream) {
-  CV_REQUIRE(dtype == CULLAVO_DT_BF16 || dtype == CULLAVO_DT_F32, CULLAVO_EUNSUPPORTED, "attention: bf16 / f32");
-  CV_REQUIRE(D == 16 || D == 32 || D == 64 || D == 128, CULLAVO_EUNSUPPORTED, "head_dim must be 16, 32, 64 or 128");
+  ATTN_REQUIRE_TYPE_AND_DIM();
   CV_REQUIRE(B >= 0 && H >= 0 && Lq >= 0, CULLAVO_EINVAL, "B, H and Lq must not be negative");
   CV_REQUIRE(past >= 0, CULLAVO_EINVAL, "past must not be negative");
   CV_REQUIRE((int64_t)past + Lq <= INT32_MAX, CULLAVO_EINVAL, "past + Lq exceeds the key index range");
-  CV_REQUIRE(ldq % 8 == 0 && ld_tok % 8 == 0 && ldo % 8 == 0, CULLAVO_EINVAL, "token strides must be multiples of 8");
-  CV_REQUIRE(ldq >= (int64_t)H * D && ld_tok >= (int64_t)H * D && ldo >= (int64_t)H * D, CULLAVO_EINVAL,
-             "token stride smaller than H*D");
-  CV_REQUIRE(ld_batch % 8 == 0, CULLAVO_EINVAL, "the cache's batch stride must be a multiple of 8");
+  ATTN_REQUIRE_CACHE_STRIDES();
   CV_REQUIRE(ld_batch >= ((int64_t)past + Lq) * ld_tok, CULLAVO_EINVAL,
              "the cache's batch stride is smaller than (past + Lq) rows");
   if (B == 0 || H == 0 || Lq == 0) return CULLAVO_OK;
   hipStream_t s = CV_STREAM(stream);
-  if (dtype == CULLAVO_DT_F32 || D < 64)
+  if (ATTN_GENERIC)
     return cullavo_attn_generic_fwd_cached(q, ldq, k_cache, v_cache, ld_tok, ld_batch, o, ldo, lse, B, H, Lq, past, D,
                                            scale, kv_start, dtype, s);
   const u16 *Q = (const u16*)q, *K = (const u16*)k_cache, *V = (const u16*)v_cache;
@@ -1495,21 +1511,17 @@ extern "C" int cullavo_attn_fwd_ragged(const void* q, int64_t ldq, const void* k
                                        int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B,
                                        int H, int Lq, const int32_t* kv_len, const int32_t* q_pad, int D,
                                        float scale, const int32_t* kv_start, int dtype, void* stream) {
-  CV_REQUIRE(dtype == CULLAVO_DT_BF16 || dtype == CULLAVO_DT_F32, CULLAVO_EUNSUPPORTED, "attention: bf16 / f32");
-  CV_REQUIRE(D == 16 || D == 32 || D == 64 || D == 128, CULLAVO_EUNSUPPORTED, "head_dim must be 16, 32, 64 or 128");
+  ATTN_REQUIRE_TYPE_AND_DIM();
   CV_REQUIRE(B >= 0 && H >= 0, CULLAVO_EINVAL, "B and H must not be negative");
   CV_REQUIRE(Lq >= 1, CULLAVO_EINVAL, "attn_fwd_ragged: Lq must be at least 1");
   CV_REQUIRE(kv_len != nullptr, CULLAVO_EINVAL, "attn_fwd_ragged: kv_len (the filled rows per sequence) is null");
-  CV_REQUIRE(ldq % 8 == 0 && ld_tok % 8 == 0 && ldo % 8 == 0, CULLAVO_EINVAL, "token strides must be multiples of 8");
-  CV_REQUIRE(ldq >= (int64_t)H * D && ld_tok >= (int64_t)H * D && ldo >= (int64_t)H * D, CULLAVO_EINVAL,
-             "token stride smaller than H*D");
-  CV_REQUIRE(ld_batch % 8 == 0, CULLAVO_EINVAL, "the cache's batch stride must be a multiple of 8");
+  ATTN_REQUIRE_CACHE_STRIDES();
   CV_REQUIRE(ld_batch >= ld_tok, CULLAVO_EINVAL, "the cache's batch stride is smaller than one row");
   if (B == 0 || H == 0) return CULLAVO_OK;
   // the rows of a sequence's slab: the bound the kernel clamps kv_len[b] to
   const int cap = (int)std::min<int64_t>(ld_batch / ld_tok, INT32_MAX - Lq);
   hipStream_t s = CV_STREAM(stream);
-  if (dtype == CULLAVO_DT_F32 || D < 64)
+  if (ATTN_GENERIC)
     return cullavo_attn_generic_fwd_ragged(q, ldq, k_cache, v_cache, ld_tok, ld_batch, o, ldo, lse, B, H, Lq, cap, D,
                                            scale, kv_start, kv_len, q_pad, dtype, s);
   const u16 *Q = (const u16*)q, *K = (const u16*)k_cache, *V = (const u16*)v_cache;
@@ -1548,16 +1560,12 @@ extern "C" int cullavo_attn_bwd_ws(const void* q, int64_t ldq, const void* k, in
                                    int64_t lddk, void* dv, int64_t lddv, int B, int H, int Lq, int Lk, int D,
                                    float scale, int causal, const int32_t* kv_start, int dtype, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-
-  CV_REQUIRE(dtype == CULLAVO_DT_BF16 || dtype == CULLAVO_DT_F32, CULLAVO_EUNSUPPORTED, "attention: bf16 / f32");
-  CV_REQUIRE(D == 16 || D == 32 || D == 64 || D == 128, CULLAVO_EUNSUPPORTED, "head_dim must be 16, 32, 64 or 128");
-  CV_REQUIRE(!causal || Lq == Lk, CULLAVO_EINVAL, "causal attention needs Lq == Lk");
-  CV_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && lddo % 8 == 0 && lddq % 8 == 0 &&
-                 lddk % 8 == 0 && lddv % 8 == 0,
-             CULLAVO_EINVAL, "token strides must be multiples of 8");
+  ATTN_REQUIRE_TYPE_AND_DIM();
+  ATTN_REQUIRE_CAUSAL_SQUARE();
+  ATTN_REQUIRE_STRIDES_X8(ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv);
   if (B == 0 || H == 0 || Lq == 0) return CULLAVO_OK;
   hipStream_t s = CV_STREAM(stream);
-  if (dtype == CULLAVO_DT_F32 || D < 64)
+  if (ATTN_GENERIC)
     return cullavo_attn_generic_bwd(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv,
                                     lddv, B, H, Lq, Lk, D, scale, causal, kv_start, dtype, s);
   const u16 *Q = (const u16*)q, *K = (const u16*)k, *V = (const u16*)v, *O = (const u16*)o, *dO = (const u16*)dout;

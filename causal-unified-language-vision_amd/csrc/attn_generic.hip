@@ -323,73 +323,52 @@ int gen_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* 
   return cullavo_check_launch("attn_bwd (generic)");
 }
 
+// f(T{}, std::integral_constant<int, D>{}) for the storage type (float, else bf16 as u16) and the head
+// dim the entry points of attention.hip hand over (theirs: f32 storage or D in {16, 32})
+template <typename F>
+int by_type_and_dim(int dtype, int D, F&& f) {
+  auto by_dim = [&](auto t) {
+    switch (D) {
+      case 16: return f(t, std::integral_constant<int, 16>{});
+      case 32: return f(t, std::integral_constant<int, 32>{});
+      case 64: return f(t, std::integral_constant<int, 64>{});
+      case 128: return f(t, std::integral_constant<int, 128>{});
+      default: break;
+    }
+    cullavo_set_error("attention: head_dim must be 16, 32, 64 or 128");
+    return (int)CULLAVO_EUNSUPPORTED;
+  };
+  return dtype == CULLAVO_DT_F32 ? by_dim(float{}) : by_dim(u16{});
+}
+
 }  // namespace
 
-// Dispatch used by cullavo_attn_fwd / _bwd (attention.hip) for f32 storage or D in {16, 32}.
 int cullavo_attn_generic_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                              void* o, int64_t ldo, float* lse, int B, int H, int Lq, int Lk, int D, float scale,
                              int causal, const int32_t* ks, int dtype, hipStream_t s) {
-#define GF(T_, D_) return gen_fwd<T_, D_>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, Lq, Lk, scale, causal, ks, s)
-#define GFD(T_)                  \
-  switch (D) {                   \
-    case 16: GF(T_, 16);         \
-    case 32: GF(T_, 32);         \
-    case 64: GF(T_, 64);         \
-    case 128: GF(T_, 128);       \
-    default: break;              \
-  }
-  if (dtype == CULLAVO_DT_F32) { GFD(float) }
-  else { GFD(u16) }
-#undef GFD
-#undef GF
-  cullavo_set_error("attention: head_dim must be 16, 32, 64 or 128");
-  return CULLAVO_EUNSUPPORTED;
+  return by_type_and_dim(dtype, D, [&](auto t, auto d) {
+    return gen_fwd<decltype(t), decltype(d)::value>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, Lq, Lk, scale, causal,
+                                                    ks, s);
+  });
 }
 
-// Dispatch used by cullavo_attn_fwd_cached (attention.hip) for f32 storage or D in {16, 32}.
 int cullavo_attn_generic_fwd_cached(const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
                                     int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B, int H,
                                     int Lq, int past, int D, float scale, const int32_t* ks, int dtype, hipStream_t s) {
-#define GC(T_, D_) \
-  return gen_fwd_cached<T_, D_>(q, ldq, k_cache, v_cache, ld_tok, ld_batch, o, ldo, lse, B, H, Lq, past, scale, ks, s)
-#define GCD(T_)                  \
-  switch (D) {                   \
-    case 16: GC(T_, 16);         \
-    case 32: GC(T_, 32);         \
-    case 64: GC(T_, 64);         \
-    case 128: GC(T_, 128);       \
-    default: break;              \
-  }
-  if (dtype == CULLAVO_DT_F32) { GCD(float) }
-  else { GCD(u16) }
-#undef GCD
-#undef GC
-  cullavo_set_error("attention: head_dim must be 16, 32, 64 or 128");
-  return CULLAVO_EUNSUPPORTED;
+  return by_type_and_dim(dtype, D, [&](auto t, auto d) {
+    return gen_fwd_cached<decltype(t), decltype(d)::value>(q, ldq, k_cache, v_cache, ld_tok, ld_batch, o, ldo, lse, B,
+                                                           H, Lq, past, scale, ks, s);
+  });
 }
 
-// Dispatch used by cullavo_attn_fwd_ragged (attention.hip) for f32 storage or D in {16, 32}.
 int cullavo_attn_generic_fwd_ragged(const void* q, int64_t ldq, const void* k_cache, const void* v_cache,
                                     int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B, int H,
                                     int Lq, int cap, int D, float scale, const int32_t* ks, const int32_t* kv_len,
                                     const int32_t* q_pad, int dtype, hipStream_t s) {
-#define GR(T_, D_)                                                                                                   \
-  return gen_fwd_ragged<T_, D_>(q, ldq, k_cache, v_cache, ld_tok, ld_batch, o, ldo, lse, B, H, Lq, cap, scale, ks, \
-                                kv_len, q_pad, s)
-#define GRD(T_)                  \
-  switch (D) {                   \
-    case 16: GR(T_, 16);         \
-    case 32: GR(T_, 32);         \
-    case 64: GR(T_, 64);         \
-    case 128: GR(T_, 128);       \
-    default: break;              \
-  }
-  if (dtype == CULLAVO_DT_F32) { GRD(float) }
-  else { GRD(u16) }
-#undef GRD
-#undef GR
-  cullavo_set_error("attention: head_dim must be 16, 32, 64 or 128");
-  return CULLAVO_EUNSUPPORTED;
+  return by_type_and_dim(dtype, D, [&](auto t, auto d) {
+    return gen_fwd_ragged<decltype(t), decltype(d)::value>(q, ldq, k_cache, v_cache, ld_tok, ld_batch, o, ldo, lse, B,
+                                                           H, Lq, cap, scale, ks, kv_len, q_pad, s);
+  });
 }
 
 int cullavo_attn_generic_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
@@ -397,21 +376,8 @@ int cullavo_attn_generic_bwd(const void* q, int64_t ldq, const void* k, int64_t 
                              float* delta, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv,
                              int B, int H, int Lq, int Lk, int D, float scale, int causal, const int32_t* ks,
                              int dtype, hipStream_t s) {
-#define GB(T_, D_)                                                                                                 \
-  return gen_bwd<T_, D_>(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv, B, H, \
-                         Lq, Lk, scale, causal, ks, s)
-#define GBD(T_)                  \
-  switch (D) {                   \
-    case 16: GB(T_, 16);         \
-    case 32: GB(T_, 32);         \
-    case 64: GB(T_, 64);         \
-    case 128: GB(T_, 128);       \
-    default: break;              \
-  }
-  if (dtype == CULLAVO_DT_F32) { GBD(float) }
-  else { GBD(u16) }
-#undef GBD
-#undef GB
-  cullavo_set_error("attention: head_dim must be 16, 32, 64 or 128");
-  return CULLAVO_EUNSUPPORTED;
+  return by_type_and_dim(dtype, D, [&](auto t, auto d) {
+    return gen_bwd<decltype(t), decltype(d)::value>(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq,
+                                                    dk, lddk, dv, lddv, B, H, Lq, Lk, scale, causal, ks, s);
+  });
 }

@@ -40,6 +40,15 @@ keeps the cache ragged while it decodes: a row stops advancing with the step tha
 eos (DecodeGraph(live=True): pos += live, start += live), so the pads a finished row is fed land on
 one scratch row behind its length and a second turn continues every conversation from exactly its
 own tokens. `length` stays the high-water mark max(lengths).
+
+How the pieces fit. lm_infer classifies a call (prefill, uniform step, ragged step) and cuts it into
+chunks; each chunk takes one attention route -- PREFILL, CACHED, RAGGED, DECODE_FUSED or DECODE,
+decided once (decode_route() reads FUSE_DECODE_ROPE per call) -- and run_chunk takes it through every
+layer (layer_infer: one ladder over the routes), the final norm and lm_head; DecodeGraph captures the
+same run_chunk. KVCache's state moves through its methods only: begin, advance / advance_ragged,
+reserve / grow, adopt (a decode graph's buffers become next_pos / lengths) and mark / release (the
+state generate() returns). generate() is one loop over a sampler (SamplerState on the device,
+HostSampler around sample_next) and a DecodeStepper (graph replay or eager cached forward).
 """
 from __future__ import annotations
 
@@ -72,8 +81,21 @@ FUSE_DECODE_ROPE = "rope" in _FUSE
 NF4_DECODE = os.environ.get("CULLAVO_NF4_DECODE", "1") != "0"
 
 
+def left_pad_span(mask, message: str):
+    """(first, count) of a 0/1 mask [B, L] (int64): each row's number of leading zeros and of ones.
+    One contiguous attended span per row, left padding only: a zero after a row's first one raises
+    NotImplementedError(message)."""
+    first = (mask.cumsum(-1) == 0).sum(-1)
+    count = mask.sum(-1)
+    if bool((count + first != mask.shape[1]).any()):
+        raise NotImplementedError(message)
+    return first, count
+
+
 class KVCache:
-    """Per-layer K, V [B, Lmax, H*D] in HBM plus the per-row state the decode kernels read."""
+    """Per-layer K, V [B, Lmax, H*D] in HBM plus the per-row state the decode kernels read. The state
+    moves through methods only: begin (prefill), advance / advance_ragged (rows appended), reserve /
+    grow (capacity), adopt / mark / release (the hand-over to a decode graph and back)."""
 
     def __init__(self, n_layers: int, B: int, max_len: int, H: int, D: int, device, dtype=torch.bfloat16):
         self.k = torch.empty((n_layers, B, max_len, H * D), dtype=dtype, device=device)
@@ -113,6 +135,45 @@ class KVCache:
         if self.kv_start is not None:
             m = m & (j >= self.kv_start[:, None])
         return m.expand(self.B, self.length)
+
+    def begin(self, kv_start, next_pos):
+        """the prefill state of an empty cache: each row's first attended key and the RoPE position
+        that follows its prompt (the prompt's rows arrive through advance(n, positions=False))"""
+        self.kv_start, self.next_pos = kv_start, next_pos
+
+    def advance(self, n: int, positions: bool = True):
+        """the bookkeeping of a uniform step that appended n rows to every sequence. positions=False:
+        next_pos is there already (begin() set it for the whole prompt; a decode graph's replay
+        advances the buffer it lent in place)"""
+        self.length += n
+        if positions:
+            self.next_pos = self.next_pos + n
+
+    def reserve(self, rows: int):
+        """room for `rows` rows per sequence, grown in 256-row steps (one copy per 256 decode steps)"""
+        if rows > self.max_len:
+            self.grow(self.max_len + 256 * -(-(rows - self.max_len) // 256))
+
+    def adopt(self, next_pos, lengths):
+        """a decode graph's buffers become next_pos and (ragged) lengths: its replays advance them in
+        place (`length` stays the high-water mark, through advance(1, positions=False))"""
+        self.next_pos = next_pos
+        if self.lengths is not None:
+            self.lengths = lengths
+
+    def mark(self):
+        """the uniform state release() rewinds to"""
+        return self.length, self.next_pos.clone()
+
+    def release(self, mark=None, fed: int = 0):
+        """the state generate() returns, out of a decode graph's buffers. Ragged: per row, every real
+        token but the row's last is cached (no row advanced on a pad). Uniform: mark() + fed rows --
+        every returned token but the last; rows a stopped batch ran past are dropped."""
+        if self.lengths is not None:
+            self.lengths, self.next_pos = self.lengths.clone(), self.next_pos.clone()
+            self.length = int(self.lengths.max())
+        else:
+            self.length, self.next_pos = mark[0] + fed, mark[1] + fed
 
     def advance_ragged(self, n_new):
         """the bookkeeping of a ragged step that appended n_new[b] (int [B]) rows to sequence b"""
@@ -166,14 +227,10 @@ class KVCache:
             else:  # the caller's text-level mask (:618-632): its leading zeros are the left padding
                 lead = (attention_mask.to(torch.int64).cumsum(-1) == 0).sum(-1).to(k0.device)
                 att &= torch.arange(L, device=k0.device)[None] >= lead[:, None]
-        am = att.to(torch.int64)
-        first = (am.cumsum(-1) == 0).sum(-1)
-        if bool((am.sum(-1) + first != L).any()):
-            raise NotImplementedError("KV-cache decode needs one contiguous attended span per sequence "
-                                      "(left padding only)")
-        cache.length = L
-        cache.kv_start = first.to(torch.int32)
-        cache.next_pos = am.sum(-1)
+        first, count = left_pad_span(att.to(torch.int64), "KV-cache decode needs one contiguous attended span per "
+                                     "sequence (left padding only)")
+        cache.begin(first.to(torch.int32), count)
+        cache.advance(L, positions=False)
         return cache
 
 
@@ -187,10 +244,8 @@ def new_chunk_padding(attention_mask, Lnew: int):
     new = attention_mask[:, -Lnew:] != 0
     if not bool((~new).any()):
         return None
-    lead = (new.to(torch.int64).cumsum(-1) == 0).sum(-1)
-    if bool((new.sum(-1) + lead != Lnew).any()):
-        raise NotImplementedError("a continuation chunk with masked tokens after a row's first attended one "
-                                  "(left padding only: the cache is compact, a hole has no row)")
+    lead, _ = left_pad_span(new.to(torch.int64), "a continuation chunk with masked tokens after a row's first "
+                            "attended one (left padding only: the cache is compact, a hole has no row)")
     return lead.to(torch.int32)
 
 
@@ -204,24 +259,38 @@ def _nf4_linear(q, x, w, group, residual=None):
     return ops.nf4_decode_linear(x, q[0], q[1], residual=residual, addend=None if t is None else t.materialize(), w=w)
 
 
-def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int, start, kv_len,
-                attn_len: int | None = None, q_pad=None):
-    """One LlamaDecoderLayer over Lnew new rows per sequence (prefill: Lnew = prompt length on an
-    empty cache; decode: Lnew = 1; continuation: Lnew > 1 on a filled cache, attending the cached
-    prefix through ops.attn_fwd_cached), appending their keys/values to the cache. No autograd.
-    attn_len: the key range decode attention is sized for (default: the filled rows + 1).
-    q_pad (int32 [B]): the ragged step -- the rows are a left-padded [B, Lnew] block, sequence b's live
-    rows go to cache rows start[b] .. (ops.kv_append_ragged) and attend with kv_len[b] = start[b] +
-    Lnew - q_pad[b] (ops.attn_fwd_ragged)."""
+# The attention routes of a chunk of new rows: decided once per chunk (by lm_infer's callees and the
+# decode graph), taken by every layer of it.
+PREFILL = "prefill"            # an empty cache: packed causal attention over the chunk's own rows
+CACHED = "cached"              # Lnew > 1 on a filled uniform cache: ops.attn_fwd_cached
+RAGGED = "ragged"              # a left-padded block on a ragged cache: kv_append_ragged + attn_fwd_ragged
+DECODE_FUSED = "decode_fused"  # one row per sequence: RoPE, append and attention in ops.attn_decode_rope
+DECODE = "decode"              # one row per sequence: ops.rope_kv_append, then ops.attn_decode
+
+
+def decode_route(dtype) -> str:
+    """the route of one new row per sequence (FUSE_DECODE_ROPE is read per call: tests patch it)"""
+    return DECODE_FUSED if FUSE_DECODE_ROPE and dtype == torch.bfloat16 else DECODE
+
+
+def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, route: str, start, kv_len=None, q_pad=None,
+                attn_len: int | None = None):
+    """One LlamaDecoderLayer over sctx.L new rows per sequence on `route`, appending their keys / values
+    to the cache at rows start[b] .. (int32 [B]). No autograd.
+    kv_len (int32 [B]): the keys a sequence attends, RAGGED (start + its live rows) and DECODE (start + 1).
+    q_pad (int32 [B]): RAGGED -- the rows are a left-padded [B, Lnew] block, sequence b's first q_pad[b]
+    rows padding. attn_len: the key range the decode routes' split-KV grid is sized for."""
     cfg = layer.cfg
     d, H, D = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim
     lg = layer.lora_groups
-    B = sctx.B
+    B, Lnew = sctx.B, sctx.L
+    # the decode rows: one per sequence, few enough for the weight-streaming products
+    gemv = Lnew == 1 and h.shape[0] <= 16 and h.dtype == torch.bfloat16
     # the layer's NF4 weight copies (quant.quantize_lm_nf4_; empty: none, or stale and dropped): the
     # decode rows' products stream 4.5 bits per weight (cullavo_nf4_decode_linear), whatever
     # FUSE_DECODE_NORMS / FUSE_DECODE_SWIGLU say; a weight left bf16 (K % 64 != 0) takes ops.linear
     nf4 = {}
-    if NF4_DECODE and Lnew == 1 and h.dtype == torch.bfloat16 and h.shape[0] <= 16:
+    if NF4_DECODE and gemv:
         from .quant import nf4_weights
         nf4 = nf4_weights(layer)
     # FUSE_DECODE_NORMS: the RMSNorms inside the q|k|v and gate|up weight-streaming products
@@ -229,8 +298,7 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int,
     # round-4 per-fragment form was ~2x slower, profiles/r04/decode/decode_fusions_ab.txt) for the
     # rows that fit LDS (M (d + 8) * 2 <= 64 KiB); FUSE_DECODE_SWIGLU: the SwiGLU in down_proj's
     # X loads (transform 2), only without FUSE_DECODE_GU. All bitwise the unfused values.
-    fused = (FUSE_DECODE_NORMS and Lnew == 1 and h.shape[0] <= 16 and h.shape[0] * (d + 8) * 2 <= 65536
-             and h.dtype == torch.bfloat16 and not nf4
+    fused = (FUSE_DECODE_NORMS and gemv and h.shape[0] * (d + 8) * 2 <= 65536 and not nf4
              and all(g is NO_LORA for g in lg.values()))
     if fused:
         qkv = ops.decode_linear(h, layer.w_qkv(), transform=1, norm_w=layer.input_layernorm.weight,
@@ -239,37 +307,33 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int,
         x1, _ = ops.rmsnorm_fwd(h, layer.input_layernorm.weight, cfg.rms_norm_eps)
         qkv = _nf4_linear(nf4.get("qkv"), x1, layer.w_qkv(), lg["qkv"])
     q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-    if q_pad is not None:
-        ops.rope(q, k, sctx.position_ids, hq=H, hk=H, head_dim=D, theta=cfg.rope_theta)
-        ops.kv_append_ragged(k, v, cache.k[li], cache.v[li], start, q_pad, B=B, Lnew=Lnew)
-        o, _ = ops.attn_fwd_ragged(q, cache.k[li], cache.v[li], kv_len, B=B, H=H, Lq=Lnew, D=D, scale=D ** -0.5,
-                                   q_pad=q_pad, kv_start=sctx.kv_start)
-    elif Lnew == 1 and qkv.dtype == torch.bfloat16 and FUSE_DECODE_ROPE:
-        # decode: RoPE, the cache append and attention in one pass (the cache row is start[b])
-        o = ops.attn_decode_rope(q, k, v, sctx.position_ids, cache.k[li], cache.v[li], start, B=B, H=H, D=D,
-                                 max_len=attn_len if attn_len is not None else cache.length + 1,
-                                 scale=D ** -0.5, theta=cfg.rope_theta, kv_start=sctx.kv_start)
-    elif Lnew == 1 and qkv.dtype == torch.bfloat16:
-        # decode: rotated k goes straight to the cache (one launch for RoPE + append)
-        ops.rope_kv_append(q, k, v, sctx.position_ids, cache.k[li], cache.v[li], start, hq=H, head_dim=D,
-                           theta=cfg.rope_theta, B=B, Lnew=1)
+    kc, vc, pos = cache.k[li], cache.v[li], sctx.position_ids
+    rope = dict(head_dim=D, theta=cfg.rope_theta)
+    attn = dict(B=B, H=H, D=D, scale=D ** -0.5, kv_start=sctx.kv_start)
+    if route == PREFILL:
+        ops.rope(q, k, pos, hq=H, hk=H, **rope)
+        ops.kv_append(k, v, kc, vc, start, B=B, Lnew=Lnew)
+        o, _ = ops.attn_fwd(q, k, v, Lq=Lnew, Lk=Lnew, causal=True, **attn)
+    elif route == CACHED:
+        # the new rows against the cached prefix and themselves, causal from the row's own position
+        ops.rope(q, k, pos, hq=H, hk=H, **rope)
+        ops.kv_append(k, v, kc, vc, start, B=B, Lnew=Lnew)
+        o, _ = ops.attn_fwd_cached(q, kc, vc, Lq=Lnew, past=cache.length, **attn)
+    elif route == RAGGED:
+        ops.rope(q, k, pos, hq=H, hk=H, **rope)
+        ops.kv_append_ragged(k, v, kc, vc, start, q_pad, B=B, Lnew=Lnew)
+        o, _ = ops.attn_fwd_ragged(q, kc, vc, kv_len, Lq=Lnew, q_pad=q_pad, **attn)
+    elif route == DECODE_FUSED:
+        o = ops.attn_decode_rope(q, k, v, pos, kc, vc, start, max_len=attn_len, theta=cfg.rope_theta, **attn)
+    elif route == DECODE:
+        if qkv.dtype == torch.bfloat16:  # rotated k goes straight to the cache (one launch for RoPE + append)
+            ops.rope_kv_append(q, k, v, pos, kc, vc, start, hq=H, B=B, Lnew=1, **rope)
+        else:
+            ops.rope(q, k, pos, hq=H, hk=H, **rope)
+            ops.kv_append(k, v, kc, vc, start, B=B, Lnew=1)
+        o = ops.attn_decode(q, kc, vc, kv_len, max_len=attn_len, **attn)
     else:
-        ops.rope(q, k, sctx.position_ids, hq=H, hk=H, head_dim=D, theta=cfg.rope_theta)
-        ops.kv_append(k, v, cache.k[li], cache.v[li], start, B=B, Lnew=Lnew)
-    if q_pad is not None:
-        pass
-    elif Lnew > 1 and cache.length > 0:
-        # continuation: the new rows against the cached prefix and themselves (their keys / values
-        # were appended just above), causal from the row's own position
-        o, _ = ops.attn_fwd_cached(q, cache.k[li], cache.v[li], B=B, H=H, Lq=Lnew, past=cache.length, D=D,
-                                   scale=D ** -0.5, kv_start=sctx.kv_start)
-    elif Lnew > 1:
-        o, _ = ops.attn_fwd(q, k, v, B=B, H=H, Lq=Lnew, Lk=Lnew, D=D, scale=D ** -0.5, causal=True,
-                            kv_start=sctx.kv_start)
-    elif not (qkv.dtype == torch.bfloat16 and FUSE_DECODE_ROPE):
-        o = ops.attn_decode(q, cache.k[li], cache.v[li], kv_len, B=B, H=H, D=D,
-                            max_len=attn_len if attn_len is not None else cache.length + 1,
-                            scale=D ** -0.5, kv_start=sctx.kv_start)
+        raise ValueError(f"layer_infer: unknown attention route {route!r}")
     h2 = _nf4_linear(nf4.get("o"), o, layer.self_attn.o_proj.weight, lg["o"], residual=h)
     if fused:
         if FUSE_DECODE_GU:  # RMSNorm, gate|up product and SwiGLU in one launch (transform 4)
@@ -288,7 +352,7 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, Lnew: int,
             a = ops.nf4_decode_linear(x2, *nf4["gu"], swiglu_out=True, w=layer.w_gu())
         else:
             a = ops.swiglu_fwd(ops.nf4_decode_linear(x2, *nf4["gu"], addend=t.materialize(), w=layer.w_gu()))
-    elif FUSE_DECODE_GU and t is None and Lnew == 1 and x2.shape[0] <= 16 and x2.dtype == torch.bfloat16:
+    elif FUSE_DECODE_GU and t is None and gemv:
         a = ops.decode_linear(x2, layer.w_gu(), transform=3)  # gate|up product + SwiGLU, one launch
     else:
         gu = ops.linear(x2, layer.w_gu(), addend=t)
@@ -362,6 +426,31 @@ class SamplerState:
                          row_offset=self.row_offset, eos_id=self.eos_token_id, pad_id=self.pad_token_id,
                          finished=self.finished, out_tokens=self.out_tokens)
 
+    def tokens(self, n: int):
+        """the first n tokens produced, [B, n]"""
+        return self.out_tokens[:, :n].clone()
+
+
+class HostSampler:
+    """SamplerState's surface for generate()'s host path: sample_next (torch ops drawing from the
+    caller's torch.Generator) plus the finished / pad bookkeeping; no kernel, no Philox state."""
+
+    def __init__(self, B: int, device, *, eos_token_id: int | None, pad_token_id: int, **warpers):
+        self.finished = torch.zeros(B, dtype=torch.bool, device=device)
+        self.next_ids, self.new = None, []
+        self.eos_token_id, self.pad_token_id, self.warpers = eos_token_id, pad_token_id, warpers
+
+    def sample(self, logits):
+        tok = sample_next(logits, **self.warpers)
+        tok = torch.where(self.finished, torch.full_like(tok, self.pad_token_id), tok)
+        self.new.append(tok)
+        if self.eos_token_id is not None:
+            self.finished |= tok == self.eos_token_id
+        self.next_ids = tok
+
+    def tokens(self, n: int):
+        return torch.stack(self.new[:n], 1)
+
 
 class DecodeGraph:
     """One cached decode step of the LM -- the new token's embedding row, every decoder layer at one
@@ -414,75 +503,110 @@ class DecodeGraph:
         finally:
             ops._TRACE["key"] = traced
         torch.cuda.current_stream(dev).wait_stream(stream)
-        cache.next_pos = self.pos  # advanced in place by every replay
-        if cache.lengths is not None:
-            cache.lengths = self.start  # likewise (cache.length: the high-water mark, by step / advance)
+        cache.adopt(self.pos, self.start)  # advanced in place by every replay
 
     def _step(self):
         lm, cache = self.lm, self.cache
-        cfg = lm.cfg
         B = cache.B
         if self.live is not None and self.sampler is not None:
             # a row advances until the step that would feed its eos: `finished` as the sampling kernel
             # left it one replay earlier, read before this step's sampling changes it
             self.live.copy_(self.sampler.finished == 0)
-        h = self.embed(self.ids[:, None]).reshape(B, cfg.hidden_size)
+        h = self.embed(self.ids[:, None]).reshape(B, lm.cfg.hidden_size)
         sctx = StepContext(B, 1, self.pos[:, None], cache.kv_start, lora_seed=0)
-        # the unfused decode attention reads kv_len = start + 1 (the fused one derives it from start)
-        kv_len = None if FUSE_DECODE_ROPE and cache.k.dtype == torch.bfloat16 else self.start + 1
-        for li, layer in enumerate(lm.model.layers):
-            h = layer_infer(layer, h, sctx, cache, li, 1, self.start, kv_len, attn_len=cache.max_len)
-        x, _ = ops.rmsnorm_fwd(h, lm.model.norm.weight, cfg.rms_norm_eps)
-        logits = ops.linear(x, lm.lm_head.weight)
+        logits = run_chunk(lm, h, sctx, cache, decode_route(cache.k.dtype), self.start, attn_len=cache.max_len)
         if self.sampler is not None:  # the next step's token, written where this graph's embedding reads it
             self.sampler.sample(logits)
-        if self.live is not None:
-            self.pos.add_(self.live)
-            self.start.add_(self.live)
-        else:
-            self.pos.add_(1)
-            self.start.add_(1)
+        n = self.live if self.live is not None else 1
+        self.pos.add_(n)
+        self.start.add_(n)
         return logits.view(B, 1, -1)
+
+    def _replay(self):
+        if self.steps_left <= 0:
+            raise ValueError("decode graph: the KV cache is full")
+        self.graph.replay()
+        self.cache.advance(1, positions=False)
+        self.steps_left -= 1
 
     def advance(self):
         """One replay of a graph with a sampler: the token the sampler holds is appended to the cache
         and the kernel at the graph's end samples the next one (no host-to-device copy, no host read)."""
         if self.sampler is None:
             raise ValueError("decode graph: advance() needs a graph captured with a sampler (use step(tokens))")
-        if self.steps_left <= 0:
-            raise ValueError("decode graph: the KV cache is full")
-        self.graph.replay()
-        self.cache.length += 1
-        self.steps_left -= 1
+        self._replay()
 
     def step(self, tokens):
         """Append `tokens` ([B] ids) to the cache and return the next logits [B, 1, V] (a view of
         the graph's output buffer, overwritten by the next replay)."""
         if self.sampler is not None:
             raise ValueError("decode graph: a graph captured with a sampler picks its own tokens (use advance())")
-        if self.steps_left <= 0:
-            raise ValueError("decode graph: the KV cache is full")
         self.ids.copy_(tokens.reshape(-1))
-        self.graph.replay()
-        self.cache.length += 1
-        self.steps_left -= 1
+        self._replay()
         return self.logits
 
 
-def _infer_rows(lm, embeds, position_ids, cache: KVCache):
-    """The decoder layers, final norm and lm_head over embeds [B, Lnew, d], appended to the cache at
-    cache.length; returns logits [B, Lnew, V]."""
+class DecodeStepper:
+    """generate()'s decode step, graph or eager behind one call: feed(sampler) appends the sampler's
+    next_ids (one token per row) to the cache and leaves the sampler holding the token after it. With
+    graph=True a DecodeGraph is captured -- around the sampling kernel when the sampler is a
+    SamplerState (advance(): no host-to-device token copy), else replayed by step(tokens) with the host
+    sampler in between; otherwise every step is model._forward_cached. compact: a finished row (its eos
+    included) is fed but does not advance (the ragged cache's `live` mask)."""
+
+    def __init__(self, model, cache: KVCache, sampler, *, graph: bool, compact: bool):
+        self.model, self.cache, self.compact = model, cache, compact
+        self.in_graph = graph and isinstance(sampler, SamplerState)
+        self.graph = None
+        if graph:
+            self.graph = DecodeGraph(model, cache, sampler=sampler if self.in_graph else None, live=compact)
+
+    def feed(self, sampler):
+        if self.in_graph:
+            return self.graph.advance()
+        live = sampler.finished == 0 if self.compact else None
+        if self.graph is not None:
+            if live is not None:
+                self.graph.live.copy_(live)
+            logits = self.graph.step(sampler.next_ids)
+        else:
+            cfg = self.model.config
+            logits = self.model._forward_cached(sampler.next_ids[:, None], None,
+                                                live[:, None].to(torch.long) if live is not None else None, None,
+                                                self.cache, None, cfg.vision_feature_layer,
+                                                cfg.vision_feature_select_strategy, None, True).logits
+        sampler.sample(logits[:, -1])
+
+
+def run_chunk(lm, h, sctx: StepContext, cache: KVCache, route: str, start, q_pad=None, live_rows=None,
+              attn_len: int | None = None):
+    """One chunk of new rows h [B * sctx.L, d] through the LM on one attention route: every decoder
+    layer, the final RMSNorm, lm_head; logits [B * sctx.L, V]. The rows' keys / values go to cache rows
+    start[b] ..; the caller advances the cache. live_rows (RAGGED): the rows sequence b really appends."""
+    kv_len = None
+    if route == RAGGED:
+        kv_len = start + live_rows
+    elif route == DECODE:  # the unfused decode attention reads its key count (the fused one derives it)
+        kv_len = start + 1
+    for li, layer in enumerate(lm.model.layers):
+        h = layer_infer(layer, h, sctx, cache, li, route, start, kv_len, q_pad, attn_len)
+    x, _ = ops.rmsnorm_fwd(h, lm.model.norm.weight, lm.cfg.rms_norm_eps)
+    return ops.linear(x, lm.lm_head.weight)
+
+
+def _infer_rows(lm, embeds, position_ids, cache: KVCache, positions: bool):
+    """A chunk embeds [B, Lnew, d] appended to a uniform cache at cache.length; logits [B, Lnew, V].
+    positions: whether the chunk moves cache.next_pos (KVCache.advance)."""
     B, Lnew, d = embeds.shape
-    cfg = lm.cfg
     sctx = StepContext(B, Lnew, position_ids, cache.kv_start, lora_seed=0)
     h = embeds.reshape(B * Lnew, d).contiguous()
     start = torch.full((B,), cache.length, dtype=torch.int32, device=h.device)
-    kv_len = start + Lnew
-    for li, layer in enumerate(lm.model.layers):
-        h = layer_infer(layer, h, sctx, cache, li, Lnew, start, kv_len)
-    cache.length += Lnew
-    x, _ = ops.rmsnorm_fwd(h, lm.model.norm.weight, cfg.rms_norm_eps)
-    logits = ops.linear(x, lm.lm_head.weight)
+    if Lnew == 1:
+        route = decode_route(h.dtype)
+    else:
+        route = CACHED if cache.length > 0 else PREFILL
+    logits = run_chunk(lm, h, sctx, cache, route, start, attn_len=cache.length + 1)
+    cache.advance(Lnew, positions)
     return logits.view(B, Lnew, -1)
 
 
@@ -491,22 +615,20 @@ def _infer_ragged(lm, embeds, q_pad, position_ids, cache: KVCache, prefill_chunk
     of sequence b are padding (q_pad None: none), appended to a cache that is, or hereby becomes,
     ragged. Returns logits [B, Lnew, V]; the padding rows' logits mean nothing."""
     B, Lnew, d = embeds.shape
-    cfg = lm.cfg
     dev = embeds.device
     cache.make_ragged()
     q_pad = (torch.zeros(B, dtype=torch.int32, device=dev) if q_pad is None
              else q_pad.to(device=dev, dtype=torch.int32))
-    # one token per sequence runs the decode kernels at start = lengths, as the decode graph does:
-    # a padding row's key / value land on the scratch row behind its length and it does not advance
+    # one token per sequence takes a decode route at start = lengths, as the decode graph does: a
+    # padding row's key / value land on the scratch row behind its length and it does not advance
     decode = Lnew == 1
-    need = cache.length + 1 if decode else int((cache.lengths + (Lnew - q_pad)).max())
-    if need > cache.max_len:  # in 256-row steps, as the decode steps grow it
-        cache.grow(cache.max_len + 256 * -(-(need - cache.max_len) // 256))
+    cache.reserve(cache.length + 1 if decode else int((cache.lengths + (Lnew - q_pad)).max()))
     if position_ids is None:
         # position next_pos[b] + i - q_pad[b] on the live rows, any finite value on the padding
         position_ids = (cache.next_pos[:, None] + torch.arange(Lnew, device=dev) - q_pad[:, None]).clamp_(min=0)
     if decode:
         position_ids = torch.where(q_pad[:, None] > 0, cache.next_pos[:, None], position_ids)
+    route = decode_route(embeds.dtype) if decode else RAGGED
     step = Lnew if prefill_chunk is None else prefill_chunk
     if step < 1:
         raise ValueError(f"prefill_chunk must be positive, got {prefill_chunk}")
@@ -517,16 +639,9 @@ def _infer_ragged(lm, embeds, q_pad, position_ids, cache: KVCache, prefill_chunk
         qp = (q_pad - c).clamp_(0, w)
         sctx = StepContext(B, w, position_ids[:, c:c + w], cache.kv_start, lora_seed=0)
         h = embeds[:, c:c + w].reshape(B * w, d).contiguous()
-        start = cache.lengths
-        kv_len = start + (w - qp)
-        for li, layer in enumerate(lm.model.layers):
-            if decode:
-                h = layer_infer(layer, h, sctx, cache, li, 1, start, start + 1, attn_len=cache.length + 1)
-            else:
-                h = layer_infer(layer, h, sctx, cache, li, w, start, kv_len, q_pad=qp)
+        logits.append(run_chunk(lm, h, sctx, cache, route, cache.lengths, qp, w - qp,
+                                attn_len=cache.length + 1).view(B, w, -1))
         cache.advance_ragged(w - qp)
-        x, _ = ops.rmsnorm_fwd(h, lm.model.norm.weight, cfg.rms_norm_eps)
-        logits.append(ops.linear(x, lm.lm_head.weight).view(B, w, -1))
     return logits[0] if len(logits) == 1 else torch.cat(logits, 1)
 
 
@@ -543,54 +658,43 @@ def lm_infer(lm, embeds, attention_mask, position_ids, cache: KVCache | None, ma
         raise NotImplementedError("KV-cache decode runs on the bf16 model (the f32 mode is a parity mode)")
     if cache is None:
         cache = KVCache(cfg.num_hidden_layers, B, max_len, cfg.num_attention_heads, cfg.head_dim, embeds.device)
-    if cache.length == 0:
+    prefill = cache.length == 0
+    if prefill:
         if Lnew > cache.max_len:  # kv_append writes rows [0, Lnew) of every sequence's cache
             raise ValueError(f"prompt of {Lnew} rows does not fit the KV cache ({cache.max_len} rows)")
         if attention_mask is None:
             attention_mask = torch.ones(B, Lnew, dtype=torch.long, device=embeds.device)
         am = attention_mask.to(torch.int64)
-        first = (am.cumsum(-1) == 0).sum(-1)
-        # contiguous valid range only: zeros may appear only before the first attended token
-        holes = (am.sum(-1) + first != Lnew)
-        if bool(holes.any()):
-            raise NotImplementedError("KV-cache generation needs left padding (no masked tokens after the "
-                                      "first attended one)")
-        cache.kv_start = first.to(torch.int32)
+        first, _ = left_pad_span(am, "KV-cache generation needs left padding (no masked tokens after the first "
+                                 "attended one)")
         if position_ids is None:
             position_ids = (am.cumsum(-1) - 1).masked_fill(am == 0, 1)
-        cache.next_pos = position_ids[:, -1].to(torch.int64) + 1
-    elif cache.lengths is not None:
-        # a ragged cache: any chunk (one token per sequence included) takes the ragged kernels
-        q_pad = new_chunk_padding(attention_mask, Lnew) if attention_mask is not None else None
-        return _infer_ragged(lm, embeds, q_pad, position_ids, cache, prefill_chunk), cache
-    elif Lnew == 1:
-        if cache.length + 1 > cache.max_len:  # room for 256 more steps (one copy per 256 steps)
-            cache.grow(cache.max_len + 256)
+        cache.begin(first.to(torch.int32), position_ids[:, -1].to(torch.int64) + 1)
+    else:
+        # a ragged cache: any chunk (one token per sequence included) takes the ragged branch. A uniform
+        # one: a 2-D mask ending in the new tokens (past + new rows, or the new ones alone) -- the cached
+        # part is the cache's own state (kv_start); zeros in the new part may only lead a row (a
+        # left-padded turn, which makes the cache ragged); all ones is the uniform step below
+        q_pad = None
+        if attention_mask is not None and (cache.lengths is not None or Lnew > 1):
+            q_pad = new_chunk_padding(attention_mask, Lnew)
+        if cache.lengths is not None or q_pad is not None:
+            return _infer_ragged(lm, embeds, q_pad, position_ids, cache, prefill_chunk), cache
+        cache.reserve(cache.length + Lnew)
         if position_ids is None:
             position_ids = cache.next_pos[:, None]
-        cache.next_pos = cache.next_pos + 1
-    else:
-        if attention_mask is not None:
-            # a 2-D mask ending in the new tokens (past + new rows, or the new ones alone): the cached
-            # part is the cache's own state (kv_start). Zeros in the new part may only lead a row (a
-            # left-padded turn, which makes the cache ragged); all ones is the uniform step below
-            q_pad = new_chunk_padding(attention_mask, Lnew)
-            if q_pad is not None:
-                return _infer_ragged(lm, embeds, q_pad, position_ids, cache, prefill_chunk), cache
-        if cache.length + Lnew > cache.max_len:  # in 256-row steps, as the decode steps grow it
-            cache.grow(cache.max_len + 256 * -(-(cache.length + Lnew - cache.max_len) // 256))
-        if position_ids is None:
-            position_ids = cache.next_pos[:, None] + torch.arange(Lnew, device=embeds.device)
-        cache.next_pos = cache.next_pos + Lnew
+            if Lnew > 1:
+                position_ids = position_ids + torch.arange(Lnew, device=embeds.device)
+    # pieces of at most prefill_chunk rows: the first on the empty cache as a plain prefill, the
+    # others as continuations (kv_start masks a sequence's left padding in every piece)
+    step = Lnew
     if prefill_chunk is not None and Lnew > prefill_chunk:
         if prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be positive, got {prefill_chunk}")
-        # pieces of at most prefill_chunk rows: the first on the empty cache as a plain prefill, the
-        # others as continuations (kv_start masks a sequence's left padding in every piece)
-        logits = [_infer_rows(lm, embeds[:, c:c + prefill_chunk], position_ids[:, c:c + prefill_chunk], cache)
-                  for c in range(0, Lnew, prefill_chunk)]
-        return torch.cat(logits, 1), cache
-    return _infer_rows(lm, embeds, position_ids, cache), cache
+        step = prefill_chunk
+    logits = [_infer_rows(lm, embeds[:, c:c + step], position_ids[:, c:c + step], cache, positions=not prefill)
+              for c in range(0, Lnew, step)]
+    return (logits[0] if len(logits) == 1 else torch.cat(logits, 1)), cache
 
 
 def sample_next(logits, *, do_sample: bool, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
