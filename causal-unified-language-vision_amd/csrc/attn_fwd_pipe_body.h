@@ -9,7 +9,8 @@
 // token stride ldk, sequence b at element offset b * ldv (ldv carries the cache's batch stride: its
 // capacity, not Lk rows). The LDS-DMA descriptors end at row Lk of the sequence's cache, so the
 // free rows behind it are never fetched: in a tile's tail they land as zeros and are masked like
-// any key >= Lk.
+// any key >= Lk. Rows below kv_start[b] never reach a result either, whatever they hold: tiles below
+// kv_start / 64 are not fetched, and the V rows of the first tile below kv_start are zeroed in LDS.
 //
 // RAGGED (attn_fwd_ragged_k, CAUSAL = CACHED = true): the kernel sets Lk = kv_len[b] and qpad =
 // q_pad[b] (both workgroup-uniform, scalar registers) before these statements, so every bound above
@@ -300,6 +301,16 @@
     if (t0 + 1 < ntiles) dma_k(t0 + 1, 1);
     __builtin_amdgcn_s_waitcnt(kVmcnt0);
     __syncthreads();
+    if constexpr (CACHED) {
+      // kv_start inside tile t0 (workgroup-uniform; absent when kv_start is null or a multiple of 64): the tile
+      // came in whole, and its rows below kv_start are cache rows the caller promises nothing about. Their
+      // scores are masked by index, but P = 0 times a NaN V row is NaN inside the P V MFMA, so those V rows
+      // become zeros here (an image row is 2 D contiguous bytes: the swizzle permutes chunks within a row).
+      // The barrier behind prep(t0) orders these stores before tile t0's transposed reads of V slot 0.
+      const int zbytes = (kstart - t0 * KT) * 2 * D;
+      for (int i = (int)threadIdx.x * 16; i < zbytes; i += 256 * 16)
+        *reinterpret_cast<u32x4*>(smem + 2 * TILE + i) = u32x4(0u);
+    }
     s_plain(std::integral_constant<int, 0>{}, sa);
     prep(t0, sa);
     __syncthreads();  // K slot 0 is refilled (tile t0 + 2) by the first iteration
