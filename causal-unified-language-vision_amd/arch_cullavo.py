@@ -16,8 +16,9 @@ from torch import nn
 
 from . import ops
 from .config import CuLLaVOConfig
-from .functions import HeadLossFn, HeadLossRowsFn, MergeFn, StepContext
+from .functions import HeadLossFn, HeadLossRowsFn, MergeFn, PackRowsFn, StepContext, UnpackRowsFn
 from .lora import NO_LORA, LoraSettings
+from .packed import check_no_holes, mask_counts, packed_plan
 from .modeling import (CLIPVisionModel, LlamaForCausalLM, LlavaMultiModalProjector, build_arenas, init_random_)
 
 
@@ -78,6 +79,9 @@ class CuLLaVOModel(nn.Module):
         # the trainer's opt-in to the supervised-row tail (forward's num_supervised); off, every caller
         # gets the full logits
         self.supervised_rows = False
+        # the trainer's opt-in to the packed step: a batch with padding runs the decoder layers and the
+        # head on its attended rows only (forward's docstring). Off, every row of [B, L] is run.
+        self.packed_rows = False
         # rows per piece of a cached forward's prefill (None: one pass; generate(prefill_chunk=N))
         self.prefill_chunk = None
 
@@ -172,10 +176,21 @@ class CuLLaVOModel(nn.Module):
     def forward(self, input_ids=None, pixel_values=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, vision_feature_layer=None, vision_feature_select_strategy=None, labels=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None,
-                num_supervised: int | None = None):
+                num_supervised: int | None = None, attended_lens=None):
         """num_supervised: host-side upper bound of the number of label positions of this batch (counted
         where the batch is built). With self.supervised_rows set (the trainer's opt-in) the loss then
-        comes from those rows only and the output carries no logits."""
+        comes from those rows only and the output carries no logits.
+        With self.packed_rows set, a batch with padding is packed: embeddings, the image merge, position
+        ids, the mask and the shifted targets are built on the padded grid as always, then the attended
+        rows are gathered sequence by sequence, the decoder layers run the varlen attention on [T, d] and
+        the head runs on those rows. loss is the padded path's (padding never carried a target); logits
+        are [B, L, V] with ZEROS at the positions that are not attended. The per-sequence attended counts
+        come to the host with the merge's own read-back; a text-only batch passes them as attended_lens
+        (host ints, counted where the batch is built, as num_supervised is; without them the batch runs
+        padded) and is trusted to have no hole in its mask. output_hidden_states and a batch without
+        padding run the padded path; a mask with a hole raises ValueError; the f32 parity mode raises
+        NotImplementedError. LoRA dropout masks are keyed by the packed row, so equality with the padded
+        run holds at dropout 0 only. With supervised_rows as well, the tail's rows are packed rows."""
         cfg = self.config
         output_hidden_states = output_hidden_states if output_hidden_states is not None else cfg.output_hidden_states
         return_dict = return_dict if return_dict is not None else cfg.use_return_dict
@@ -189,15 +204,20 @@ class CuLLaVOModel(nn.Module):
             raise NotImplementedError("flash attention never materialises attention probabilities")
 
         self.vision_tower.eval()  # :578 (no dropout in this tower; kept for parity of intent)
+        if self.packed_rows and self.dtype != torch.bfloat16:
+            raise NotImplementedError("packed_rows runs the bf16 varlen attention; the f32 parity mode is not packed")
 
         if inputs_embeds is None:
             B, S = input_ids.shape
             inputs_embeds = self.get_input_embeddings()(input_ids)  # :582
             if pixel_values is not None and S != 1:
-                stats = self._merge_stats_async(input_ids)  # read back while the tower runs
+                # read back while the tower runs (packed step: the per-row counts ride along)
+                stats = self._merge_stats_async(input_ids, attention_mask if self.packed_rows else None)
                 image_features = self._image_features(pixel_values, vision_feature_layer, strategy)  # :586-599
                 inputs_embeds, attention_mask, position_ids = self._merge(image_features, inputs_embeds, input_ids,
                                                                           attention_mask, stats)  # :600-602
+                if self.packed_rows:
+                    attended_lens = self._merged_lens(stats[0], B, image_features.shape[1])
                 if labels is None:  # :603-604
                     labels = torch.full_like(attention_mask, cfg.ignore_index).to(torch.long)
         B, L, d = inputs_embeds.shape
@@ -206,6 +226,10 @@ class CuLLaVOModel(nn.Module):
         kv_start = None
         if attention_mask is not None:
             kv_start = (attention_mask.cumsum(-1) == 0).sum(-1).to(torch.int32)
+        plan = self._packed_plan(attention_mask, attended_lens, B, L, output_hidden_states)
+        if plan is not None:
+            return self._forward_packed(inputs_embeds, labels, attention_mask, position_ids, plan, num_supervised,
+                                        return_dict)
         sctx = StepContext(B, L, position_ids, kv_start)
         lm = self.language_model
         n_rows = self._tail_rows(num_supervised, labels, B, L, output_hidden_states)
@@ -234,6 +258,69 @@ class CuLLaVOModel(nn.Module):
             out = (logits,) + ((hs_t,) if hs_t is not None else ())
             return (loss,) + out if loss is not None else out
         return CullavoCausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=None, hidden_states=hs_t,
+                                             attentions=None)
+
+    # -- packed step: only the attended rows run the decoder layers and the head ------------------
+    @staticmethod
+    def _merged_lens(host, B: int, P: int):
+        """attended rows per sequence after the merge, from the read-back of _merge_stats_async (already
+        waited for by _merge): every attended <image> token became P rows. Raises on a mask with a hole."""
+        img, count, span = (host[3 + i * B:3 + (i + 1) * B].tolist() for i in range(3))
+        check_no_holes(count, span)
+        return [c + n * (P - 1) for c, n in zip(count, img)]
+
+    def _packed_plan(self, attention_mask, attended_lens, B: int, L: int, output_hidden_states):
+        """the batch's PackedPlan, or None for the padded path (switch off, no mask or no host-side counts,
+        hidden states wanted, or a batch without padding)"""
+        if not self.packed_rows or attention_mask is None or attended_lens is None or output_hidden_states:
+            return None
+        if tuple(attention_mask.shape) != (B, L) or sum(int(n) for n in attended_lens) >= B * L:
+            return None
+        return packed_plan(attention_mask, attended_lens)
+
+    def _forward_packed(self, inputs_embeds, labels, attention_mask, position_ids, plan, num_supervised, return_dict):
+        cfg, lm = self.config, self.language_model
+        B, L, d = inputs_embeds.shape
+        rows = plan.rows
+        live = rows >= 0
+        pos = torch.where(live, position_ids.reshape(-1)[rows.clamp_min(0)], 0)
+        sctx = StepContext(B, L, pos)
+        sctx.packed = plan
+        h = PackRowsFn.apply(inputs_embeds.reshape(B * L, d), rows)
+        targets = None
+        if labels is not None:
+            if labels.shape != (B, L):
+                raise IndexError(f"The shape of the mask [{B}, {L - 1}] at index 1 does not match the shape of "
+                                 f"the indexed tensor [{labels.shape[0]}, {labels.shape[-1] - 1}] at index 1")
+            targets = ops.gather_targets(ops.shift_targets(labels, attention_mask, cfg.ignore_index), rows,
+                                         cfg.ignore_index)
+        n_rows = 0  # the supervised-row tail on top: its rows are packed rows (sized as _tail_rows sizes them)
+        if self.supervised_rows and num_supervised is not None and labels is not None:
+            n = max(8, -(-int(num_supervised) // 8) * 8)
+            n_rows = n if n < plan.Tp else 0
+        if n_rows:
+            sup = ops.supervised_rows(targets, n_rows, cfg.ignore_index)
+            last = lm.model.layers[-1]
+            compact = all(last.lora_groups[g] is NO_LORA for g in ("gu", "down"))
+            if compact:
+                sctx.tail_layer, sctx.tail_rows = last, sup
+            h, _ = lm.decode(h, sctx, False)
+            for ar in self.arenas.values():
+                ar.wait_update()
+            loss = HeadLossRowsFn.apply(h, lm, targets, cfg.ignore_index, sup, plan.Tp, compact, *lm.head_params())
+            logits = None
+        else:
+            h, _ = lm.decode(h, sctx, False)
+            for ar in self.arenas.values():  # final norm / lm_head: pending optimizer updates
+                ar.wait_update()
+            if targets is not None:
+                loss, logits = HeadLossFn.apply(h, lm, targets, cfg.ignore_index, *lm.head_params())
+            else:
+                loss, logits = None, lm.lm_head(lm.model.norm(h))
+            logits = UnpackRowsFn.apply(logits, rows, B * L).view(B, L, -1)  # zeros where nothing is attended
+        if not return_dict:
+            return (loss, logits) if loss is not None else (logits,)
+        return CullavoCausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=None, hidden_states=None,
                                              attentions=None)
 
     # -- supervised-row tail: the training step's loss without the rows that carry no label ------
@@ -416,7 +503,7 @@ class CuLLaVOModel(nn.Module):
             raise ValueError(f"Unexpected select feature strategy: {self.config.vision_feature_select_strategy}")
         return self.multi_modal_projector(feats)
 
-    def _merge_stats_async(self, input_ids):
+    def _merge_stats_async(self, input_ids, attention_mask=None):
         """The three integers that size the merge (max image tokens per row, total image
         tokens, rows ending in <pad>), reduced on the GPU and copied to pinned host memory
         without waiting: the copy completes long before the vision tower enqueued behind it,
@@ -424,7 +511,12 @@ class CuLLaVOModel(nn.Module):
         cfg = self.config
         is_img = input_ids == cfg.image_token_index
         st = torch.stack([is_img.sum(-1).max(), is_img.sum(), (input_ids[:, -1] == cfg.pad_token_id).sum()])
-        host = torch.empty(3, dtype=st.dtype, pin_memory=True)
+        if attention_mask is not None:
+            # the packed step's per-row counts in the same copy: attended <image> tokens, attended
+            # positions and their span (packed.mask_counts)
+            cs = mask_counts(attention_mask)
+            st = torch.cat([st, (is_img & (attention_mask != 0)).sum(-1), cs[0], cs[1]])
+        host = torch.empty(st.numel(), dtype=st.dtype, pin_memory=True)
         host.copy_(st, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -439,7 +531,7 @@ class CuLLaVOModel(nn.Module):
         B, S = input_ids.shape
         host, ev = stats if stats is not None else self._merge_stats_async(input_ids)
         ev.synchronize()
-        n_max, n_total, n_pad_last = (int(x) for x in host.tolist())
+        n_max, n_total, n_pad_last = (int(x) for x in host[:3].tolist())
         if n_total != n_img:
             raise ValueError(f"The input provided to the model are wrong. The number of image tokens is {n_total} "
                              f"while the number of image given to the model is {n_img}. This prevents correct "

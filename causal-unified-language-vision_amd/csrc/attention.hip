@@ -15,6 +15,8 @@
 // results are bitwise reproducible.
 #include "common.h"
 
+#include <vector>
+
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 frag8;
@@ -222,6 +224,40 @@ struct StageDMA1 {
     for (int i = 0; i < kPer; ++i) lds_dma16s(rs, lds + (wave + NW * i) * 1024, vo, (int)(i * NW * kRP * ld * 2));
   }
 };
+
+// Which rows a kernel's sequences own. The backward kernels take it in kv_start's place (a trailing
+// template argument SEQ; attn_bwd_dkdv8_k through its included body), as one of
+//   const int32_t*  the uniform [B, L] grid: sequence b owns rows b L .. b L + L - 1, the pointer is
+//                   kv_start (keys below kv_start[b] are masked; null = none);
+//   VarSeq          sequences of unequal length packed back to back (cullavo_attn_*_varlen):
+//                   sequence b owns rows start[b] .. start[b] + len[b] - 1, the grid and the lse /
+//                   delta rows are sized by max_len, and there is no kv_start.
+// The uniform overloads return the kernel's own arguments, so those instantiations compile to the
+// code they were before the varlen ones existed (tools/isa_diff.py). len[b] is a device value the
+// host cannot check: it is clamped to [0, max_len], so no value indexes lse / delta or the dS^T
+// workspace outside sequence b's part. All loads are from workgroup-uniform addresses.
+struct VarSeq {
+  const int32_t* start;
+  const int32_t* len;
+  int max_len;
+};
+template <class SEQ>
+constexpr bool kVarlen = std::is_same<SEQ, VarSeq>::value;
+DEV int seq_grid_rows(const int32_t*, int L) { return L; }          // rows the grid / lse stride covers
+DEV int seq_grid_rows(const VarSeq& s, int) { return s.max_len; }
+DEV int seq_grid_rows(int L) { return L; }                          // (attn_delta_k: L in the SEQ's place)
+DEV int seq_grid_rows(const VarSeq& s) { return s.max_len; }
+DEV int seq_rows(const int32_t*, int, int L) { return L; }          // rows of sequence b
+DEV int seq_rows(const VarSeq& s, int b, int) { return min(max(s.len[b], 0), s.max_len); }
+DEV int64_t seq_row0(const int32_t*, int b, int L) { return (int64_t)b * L; }  // its first row
+DEV int64_t seq_row0(const VarSeq& s, int b, int) { return s.start[b]; }
+DEV int seq_kstart(const int32_t* ks, int b) { return ks ? ks[b] : 0; }
+DEV int seq_kstart(const VarSeq&, int) { return 0; }
+// the kernel argument's type: the uniform grid's kv_start keeps its __restrict__
+template <class SEQ>
+struct SeqArg { using type = SEQ; };
+template <>
+struct SeqArg<const int32_t*> { using type = const int32_t* __restrict__; };
 
 // row of accumulator register r of a 32x32 tile for lane half h
 DEV int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
@@ -577,8 +613,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_k(const u16* __restrict_
                                                           u16* __restrict__ O, int64_t ldo,
                                                           float* __restrict__ LSE, int H, int Lq, int Lk,
                                                           float scale, const int32_t* __restrict__ kv_start) {
-  constexpr bool CACHED = false, RAGGED = false;
-  constexpr int qpad = 0;
+  constexpr bool CACHED = false, RAGGED = false, VARLEN = false;
+  constexpr int qpad = 0, vl_max = 0, vl_row0 = 0;
 #include "attn_fwd_pipe_body.h"
 }
 
@@ -593,8 +629,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_cached_k(const u16* __restric
                                                             u16* __restrict__ O, int64_t ldo,
                                                             float* __restrict__ LSE, int H, int Lq, int Lk,
                                                             float scale, const int32_t* __restrict__ kv_start) {
-  constexpr bool CAUSAL = true, CACHED = true, RAGGED = false;
-  constexpr int qpad = 0;
+  constexpr bool CAUSAL = true, CACHED = true, RAGGED = false, VARLEN = false;
+  constexpr int qpad = 0, vl_max = 0, vl_row0 = 0;
 #include "attn_fwd_pipe_body.h"
 }
 
@@ -613,10 +649,36 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_ragged_k(const u16* __restric
                                                             float scale, const int32_t* __restrict__ kv_start,
                                                             const int32_t* __restrict__ kv_len,
                                                             const int32_t* __restrict__ q_pad) {
-  constexpr bool CAUSAL = true, CACHED = true, RAGGED = true;
+  constexpr bool CAUSAL = true, CACHED = true, RAGGED = true, VARLEN = false;
+  constexpr int vl_max = 0, vl_row0 = 0;
   const int seq = xcd_remap(blockIdx.x, gridDim.x) / ((Lq + 127) / 128) / H;  // the body's b
   const int Lk = min(max(kv_len[seq], 0), cap);
   const int qpad = q_pad ? min(max(q_pad[seq], 0), Lq) : 0;
+#include "attn_fwd_pipe_body.h"
+}
+
+// attn_fwd_pipe_k<D, true> over sequences of unequal length packed back to back
+// (cullavo_attn_fwd_varlen): sequence b owns rows seq_start[b] .. seq_start[b] + seq_len[b] - 1 of
+// Q / K / V / O, the grid and the [B, H, vl_max] lse are sized by the host's bound vl_max.
+// seq_len[b] is clamped to [0, vl_max] (a device value: see VarSeq). A workgroup whose query tile
+// starts at or beyond the sequence's end exits: workgroup-uniform, before any barrier.
+template <int D>
+__global__ __launch_bounds__(256, 2) void attn_fwd_varlen_k(const u16* __restrict__ Q, int64_t ldq,
+                                                            const u16* __restrict__ K, int64_t ldk,
+                                                            const u16* __restrict__ V, int64_t ldv,
+                                                            u16* __restrict__ O, int64_t ldo,
+                                                            float* __restrict__ LSE, int H, int vl_max, float scale,
+                                                            const int32_t* __restrict__ seq_start,
+                                                            const int32_t* __restrict__ seq_len) {
+  constexpr bool CAUSAL = true, CACHED = false, RAGGED = false, VARLEN = true;
+  constexpr int qpad = 0;
+  constexpr const int32_t* kv_start = nullptr;
+  const int vl_nqb = (vl_max + 127) / 128;
+  const int vl_lid = xcd_remap(blockIdx.x, gridDim.x);  // the body's lid, qb and b
+  const int seq = vl_lid / vl_nqb / H;
+  const int Lq = min(max(seq_len[seq], 0), vl_max), Lk = Lq;
+  if ((vl_nqb - 1 - vl_lid % vl_nqb) * 128 >= Lq) return;
+  const int64_t vl_row0 = seq_start[seq];
 #include "attn_fwd_pipe_body.h"
 }
 
@@ -624,18 +686,30 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_ragged_k(const u16* __restric
 // backward
 // ============================================================================================
 // delta[b,h,q] = sum_d dO*O  (f32); one 16-lane group per (token, head) row for D=128
-template <int D>
+// (SEQ: the rows per sequence L, or a VarSeq; the varlen form runs over B max_len rows, reads row
+// t < len[b] of sequence b at start[b] + t and skips the rest)
+template <int D, class SEQ = int>
 __global__ __launch_bounds__(256) void attn_delta_k(const u16* __restrict__ O, int64_t ldo,
                                                     const u16* __restrict__ dO, int64_t lddo,
-                                                    float* __restrict__ delta, int B, int H, int L) {
+                                                    float* __restrict__ delta, int B, int H, SEQ sq) {
   constexpr int LPR = D / 8;  // lanes per row
+  const int L = seq_grid_rows(sq);
   const int64_t row = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LPR;  // (b, t, h) row
   const int sub = threadIdx.x % LPR;
-  const int64_t nrows = (int64_t)B * L * H;
+  int64_t nrows = (int64_t)B * L * H;
+  int64_t src = 0;  // varlen: the packed row of (b, t)
+  if constexpr (kVarlen<SEQ>) {
+    if (row < nrows) {
+      const int64_t bt = row / H;
+      const int bb = (int)(bt / L), t = (int)(bt % L);
+      if (t < seq_rows(sq, bb, L)) src = seq_row0(sq, bb, L) + t;
+      else nrows = 0;  // a row past the sequence's end: nothing read, nothing written
+    }
+  }
   float acc = 0.f;
   if (row < nrows) {
     const int hh = (int)(row % H);
-    const int64_t bt = row / H;
+    const int64_t bt = kVarlen<SEQ> ? src : row / H;
     float a[8], d[8];
     load8(O + bt * ldo + (int64_t)hh * D + sub * 8, a);
     load8(dO + bt * lddo + (int64_t)hh * D + sub * 8, d);
@@ -656,13 +730,13 @@ __global__ __launch_bounds__(256) void attn_delta_k(const u16* __restrict__ O, i
 // 32-row query tiles staged in LDS. S = Q K^T and dP = dO V^T keep the key on the lane;
 // dV = P^T dO and dK = dS^T Q take P / dS straight from the accumulators (A operand) and
 // dO / Q as transposed LDS fragments.
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, class SEQ = const int32_t*>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_k(
     const u16* __restrict__ Q, int64_t ldq, const u16* __restrict__ K, int64_t ldk,
     const u16* __restrict__ V, int64_t ldv, const u16* __restrict__ dO, int64_t lddo,
     const float* __restrict__ LSE, const float* __restrict__ DELTA, u16* __restrict__ dK,
-    int64_t lddk, u16* __restrict__ dV, int64_t lddv, int H, int Lq, int Lk, float scale,
-    const int32_t* __restrict__ kv_start) {
+    int64_t lddk, u16* __restrict__ dV, int64_t lddv, int H, int LqG, int LkG, float scale,
+    typename SeqArg<SEQ>::type kv_start) {
   constexpr int QT = 32;         // query rows per tile (64-row tiles lost the sweep on both head dims)
   constexpr int NSUB = QT / 32;  // 32-row query sub-tiles per barrier
   constexpr int TILE = QT * D * 2;
@@ -674,20 +748,22 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_k(
 
   // 1-D grid of (key block, head, batch), XCD-remapped: the key blocks of one (b, h) share
   // its Q / dO tiles in one XCD's L2
-  const int nkb = (Lk + 127) / 128;
+  const int nkb = (seq_grid_rows(kv_start, LkG) + 127) / 128;
   const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int kb = lid % nkb, hb = lid / nkb;
   const int h = hb % H, b = hb / H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hf = lane >> 5;
   const int key = kb * 128 + wave * 32 + (lane & 31);  // this lane's key (operand column)
-  const int kstart = kv_start ? kv_start[b] : 0;
+  const int kstart = seq_kstart(kv_start, b);
+  const int Lq = seq_rows(kv_start, b, LqG), Lk = seq_rows(kv_start, b, LkG);  // this sequence's rows
+  if constexpr (kVarlen<SEQ>) if (kb * 128 >= Lk) return;  // a tile past the sequence's end (workgroup-uniform)
 
-  const u16* Qb = Q + (int64_t)b * Lq * ldq + (int64_t)h * D;
-  const u16* dOb = dO + (int64_t)b * Lq * lddo + (int64_t)h * D;
-  const u16* Kb = K + (int64_t)b * Lk * ldk + (int64_t)h * D;
-  const u16* Vb = V + (int64_t)b * Lk * ldv + (int64_t)h * D;
-  const float* lseb = LSE + ((int64_t)b * H + h) * Lq;
-  const float* delb = DELTA + ((int64_t)b * H + h) * Lq;
+  const u16* Qb = Q + seq_row0(kv_start, b, LqG) * ldq + (int64_t)h * D;
+  const u16* dOb = dO + seq_row0(kv_start, b, LqG) * lddo + (int64_t)h * D;
+  const u16* Kb = K + seq_row0(kv_start, b, LkG) * ldk + (int64_t)h * D;
+  const u16* Vb = V + seq_row0(kv_start, b, LkG) * ldv + (int64_t)h * D;
+  const float* lseb = LSE + ((int64_t)b * H + h) * seq_grid_rows(kv_start, LqG);
+  const float* delb = DELTA + ((int64_t)b * H + h) * seq_grid_rows(kv_start, LqG);
 
   frag8 kf[NS], vf[NS];
 #pragma unroll
@@ -807,8 +883,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_k(
       const int kk = kb * 128 + wave * 32 + acc_row(r, hf);
       if (kk < Lk) {
         const int d = dt * 32 + (lane & 31);
-        dK[((int64_t)b * Lk + kk) * lddk + (int64_t)h * D + d] = f2bf(dk[dt][r] * scale);
-        dV[((int64_t)b * Lk + kk) * lddv + (int64_t)h * D + d] = f2bf(dv[dt][r]);
+        dK[(seq_row0(kv_start, b, LkG) + kk) * lddk + (int64_t)h * D + d] = f2bf(dk[dt][r] * scale);
+        dV[(seq_row0(kv_start, b, LkG) + kk) * lddv + (int64_t)h * D + d] = f2bf(dv[dt][r]);
       }
     }
 }
@@ -816,31 +892,33 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_k(
 // Kernel B: dQ. A wave owns 32 query rows (Q, dO fragments in registers, lse/delta per
 // lane); the workgroup sweeps 32-key K/V tiles. S^T = K Q^T, dP^T = V dO^T (query on the
 // lane), dQ^T += K^T dS^T with K^T as a transposed LDS fragment.
-template <int D, bool CAUSAL, int KT>
+template <int D, bool CAUSAL, int KT, class SEQ = const int32_t*>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dq_k(
     const u16* __restrict__ Q, int64_t ldq, const u16* __restrict__ K, int64_t ldk,
     const u16* __restrict__ V, int64_t ldv, const u16* __restrict__ dO, int64_t lddo,
     const float* __restrict__ LSE, const float* __restrict__ DELTA, u16* __restrict__ dQ,
-    int64_t lddq, int H, int Lq, int Lk, float scale, const int32_t* __restrict__ kv_start) {
+    int64_t lddq, int H, int LqG, int LkG, float scale, typename SeqArg<SEQ>::type kv_start) {
   constexpr int TILE = KT * D * 2;
   constexpr int NSUB = KT / 32;  // 32-key sub-tiles per barrier
   constexpr int NS = D / 16;
   constexpr int ND = D / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  const int nqb = (Lq + 127) / 128;
+  const int nqb = (seq_grid_rows(kv_start, LqG) + 127) / 128;
   const int lid = xcd_remap(blockIdx.x, gridDim.x);  // as attn_fwd_k: one (b, h) per XCD range
   const int qi = lid % nqb, hb = lid / nqb;
   const int qb = CAUSAL ? (nqb - 1 - qi) : qi;
   const int h = hb % H, b = hb / H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hf = lane >> 5;
   const int q = qb * 128 + wave * 32 + (lane & 31);
-  const int kstart = kv_start ? kv_start[b] : 0;
+  const int kstart = seq_kstart(kv_start, b);
+  const int Lq = seq_rows(kv_start, b, LqG), Lk = seq_rows(kv_start, b, LkG);  // this sequence's rows
+  if constexpr (kVarlen<SEQ>) if (qb * 128 >= Lq) return;  // a tile past the sequence's end (workgroup-uniform)
 
-  const u16* Qb = Q + (int64_t)b * Lq * ldq + (int64_t)h * D;
-  const u16* dOb = dO + (int64_t)b * Lq * lddo + (int64_t)h * D;
-  const u16* Kb = K + (int64_t)b * Lk * ldk + (int64_t)h * D;
-  const u16* Vb = V + (int64_t)b * Lk * ldv + (int64_t)h * D;
+  const u16* Qb = Q + seq_row0(kv_start, b, LqG) * ldq + (int64_t)h * D;
+  const u16* dOb = dO + seq_row0(kv_start, b, LqG) * lddo + (int64_t)h * D;
+  const u16* Kb = K + seq_row0(kv_start, b, LkG) * ldk + (int64_t)h * D;
+  const u16* Vb = V + seq_row0(kv_start, b, LkG) * ldv + (int64_t)h * D;
 
   frag8 qf[NS], of[NS];
 #pragma unroll
@@ -849,8 +927,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_k(
     qf[s] = __builtin_bit_cast(frag8, ok ? *reinterpret_cast<const u16x8*>(Qb + (int64_t)q * ldq + 16 * s + 8 * hf) : u16x8(0));
     of[s] = __builtin_bit_cast(frag8, ok ? *reinterpret_cast<const u16x8*>(dOb + (int64_t)q * lddo + 16 * s + 8 * hf) : u16x8(0));
   }
-  const float lse2 = (q < Lq) ? LSE[((int64_t)b * H + h) * Lq + q] * kLog2e : INFINITY;
-  const float del = (q < Lq) ? DELTA[((int64_t)b * H + h) * Lq + q] : 0.f;
+  const float lse2 = (q < Lq) ? LSE[((int64_t)b * H + h) * seq_grid_rows(kv_start, LqG) + q] * kLog2e : INFINITY;
+  const float del = (q < Lq) ? DELTA[((int64_t)b * H + h) * seq_grid_rows(kv_start, LqG) + q] : 0.f;
   const float c = scale * kLog2e;
   f32x16 dq[ND];
 #pragma unroll
@@ -916,7 +994,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_k(
     __syncthreads();
   }
   if (q < Lq) {
-    u16* dQb = dQ + ((int64_t)b * Lq + q) * lddq + (int64_t)h * D;
+    u16* dQb = dQ + (seq_row0(kv_start, b, LqG) + q) * lddq + (int64_t)h * D;
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
@@ -971,244 +1049,31 @@ struct StageN {
 // register-staged form, bitwise equal (profiles/r05/attn/attn_bwd_stage_ab.txt). DS_OUT: also store
 // dS^T[b, h][key][q] for attn_bwd_dq_ds_k (mode 7); the workspace is row-major, ldst = LqP with
 // the 128-query block qb at column 128 qb (st_blk = 128).
+// The kernel's statements are in attn_bwd_dkdv8_body.h, shared with attn_bwd_dkdv8_varlen_k below (text,
+// not a function both call: inlined through a function attn_bwd_dkdv8_k<128, true, true> came out 142
+// instructions longer).
 template <int D, bool CAUSAL, bool DS_OUT>
 __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_k(
     const u16* __restrict__ Q, int64_t ldq, const u16* __restrict__ K, int64_t ldk,
     const u16* __restrict__ V, int64_t ldv, const u16* __restrict__ dO, int64_t lddo,
     const float* __restrict__ LSE, const float* __restrict__ DELTA, u16* __restrict__ dK,
-    int64_t lddk, u16* __restrict__ dV, int64_t lddv, int H, int Lq, int Lk, float scale,
+    int64_t lddk, u16* __restrict__ dV, int64_t lddv, int H, int LqG, int LkG, float scale,
     const int32_t* __restrict__ kv_start, u16* __restrict__ dST, int64_t ldst, int64_t st_bh, int64_t st_blk) {
-  constexpr int QT = 64, KB = 128;
-  constexpr int TQ = QT * D * 2;          // bytes of a Q (or dO) tile
-  constexpr int TK = KB * D * 2;          // bytes of the K (or V) image
-  constexpr int NS = D / 16;
-  constexpr int ND = D / 32;
-  constexpr int BUF = 2 * TQ + 2 * QT * 4;  // [Q | dO | lse(64) | delta(64)]
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* sK = smem;
-  char* sV = smem + TK;
-  char* bufs = smem + 2 * TK;
-
-  const int nkb = (Lk + KB - 1) / KB;
-  const int lid = xcd_remap(blockIdx.x, gridDim.x);
-  const int kb = lid % nkb, hb = lid / nkb;
-  const int h = hb % H, b = hb / H;
-  // wave index through readfirstlane: wave-uniform to the compiler (scalar slice / half branches
-  // and row bases)
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hf = lane >> 5;
-  const int ksl = wave & 3, u = wave >> 2;          // 32-key slice, query half of each tile
-  const int key = kb * KB + ksl * 32 + (lane & 31);  // this lane's key
-  const int kstart = kv_start ? kv_start[b] : 0;
-  // live queries of this key: [qlo, qlim) (empty for keys before kstart or past Lk)
-  const int qlo = CAUSAL ? key : 0;
-  const int qlim = (key < kstart || key >= Lk) ? qlo : Lq;
-  const unsigned qspan = (unsigned)max(qlim - qlo, 0);
-
-  const u16* Qb = Q + (int64_t)b * Lq * ldq + (int64_t)h * D;
-  const u16* dOb = dO + (int64_t)b * Lq * lddo + (int64_t)h * D;
-  const u16* Kb = K + (int64_t)b * Lk * ldk + (int64_t)h * D;
-  const u16* Vb = V + (int64_t)b * Lk * ldv + (int64_t)h * D;
-  const float* lseb = LSE + ((int64_t)b * H + h) * Lq;
-  const float* delb = DELTA + ((int64_t)b * H + h) * Lq;
-
-  f32x16 dk[ND], dv[ND];
-#pragma unroll
-  for (int i = 0; i < ND; ++i) { dk[i] = f32x16(0.f); dv[i] = f32x16(0.f); }
-  const float c = scale * kLog2e;
-  const int kmin = kb * KB;
-  const int qt0 = CAUSAL ? (kmin / QT) : 0;
-  const int nqt = (Lq + QT - 1) / QT;
-  const bool block_live = kmin < Lk && (kmin + KB > kstart);
-
-  // Q / dO tiles by LDS-DMA into the swizzled image (as the forward's StageDMA)
-  StageDMA<QT, D, 8> dq_, ddo_;
-  dq_.prep(ldq, wave, lane);
-  ddo_.prep(lddo, wave, lane);
-  // per-lane LDS byte offsets of the asm fragment reads (rows relative to a 32-row slice / a
-  // 16-key slice: the image swizzle depends on row & 15 only)
-  unsigned roff_b[NS], toff_b[ND][2];
-  {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) roff_b[s] = kv_off<D>(lane & 31, 2 * s + (lane >> 5));
-    const int i = lane & 15, qq = i >> 2, pp = i & 3;
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt) {
-      const int ch = ((dt * 32 + 16 * ((lane >> 4) & 1)) >> 3) + (pp >> 1);
-      toff_b[dt][0] = kv_off<D>(4 * hf + qq, ch) + 8 * (pp & 1);
-      toff_b[dt][1] = kv_off<D>(4 * hf + qq + 8, ch) + 8 * (pp & 1);
-    }
-  }
-  float aux = 0.f;
-  // the next tile's lse / delta: loaded raw and first used when staged after the tile's compute
-  // (the lse * log2 e at load time made the compiler wait for the load -- and for the in-flight
-  // Q / dO prefetch -- at the top of every tile)
-  bool aux_in = false;
-  auto load_aux = [&](int qt) {
-    if (threadIdx.x < 2 * QT) {
-      const int qq = qt * QT + (int)threadIdx.x % QT;
-      aux_in = qq < Lq;
-      aux = (threadIdx.x < QT ? lseb : delb)[min(qq, Lq - 1)];
-    }
-  };
-  auto store_aux = [&](char* buf) {
-    if (threadIdx.x < 2 * QT)
-      ((float*)(buf + 2 * TQ))[threadIdx.x] =
-          threadIdx.x < QT ? (aux_in ? aux * kLog2e : INFINITY) : (aux_in ? aux : 0.f);
-  };
-  if (block_live) {
-    StageN<KB, D, 512> skv;
-    skv.load(Kb, ldk, kmin, Lk);
-    skv.store(sK);
-    skv.load(Vb, ldv, kmin, Lk);
-    skv.store(sV);
-    if (qt0 < nqt) {
-      dq_.issue(Qb, ldq, qt0 * QT, Lq, bufs, wave);
-      ddo_.issue(dOb, lddo, qt0 * QT, Lq, bufs + TQ, wave);
-      load_aux(qt0);
-      store_aux(bufs);
-    }
-  }
-  __builtin_amdgcn_s_waitcnt(kVmcnt0);  // see attn_fwd_k: keeps hipcc from waiting on the prefetch
-  __syncthreads();
-
-  for (int qt = qt0; block_live && qt < nqt; ++qt) {
-    const int cur = (qt - qt0) & 1;
-    char* buf = bufs + cur * BUF;
-    char* nbuf = bufs + (cur ^ 1) * BUF;
-    const bool more = qt + 1 < nqt;
-    if (more) {
-      dq_.issue(Qb, ldq, (qt + 1) * QT, Lq, nbuf, wave);  // nbuf was last read before the previous barrier
-      ddo_.issue(dOb, lddo, (qt + 1) * QT, Lq, nbuf + TQ, wave);
-      load_aux(qt + 1);
-    }
-    const float* slse = (const float*)(buf + 2 * TQ);
-    const float* sdel = slse + QT;
-    // S[q][key], dP[q][key] for this wave's 32 query rows of the tile
-    f32x16 sacc = f32x16(0.f), pacc = f32x16(0.f);
-    {
-      // inline-asm fragment reads (a compiler-visible LDS read may alias the next tile's in-flight
-      // LDS-DMA, so hipcc would wait vmcnt(0) in front of it), one k-step ahead of the MFMAs: the
-      // four reads of step s + 1 are in flight while step s's two MFMAs issue
-      const unsigned aq = lds_addr(buf) + 2u * D * 32u * u, ak = lds_addr(sK) + 2u * D * 32u * ksl;
-      s16x8 q0, k0, d0, v0, q1, k1, d1, v1;
-      __builtin_amdgcn_sched_barrier(0);
-      rd4(q0, k0, d0, v0, aq + roff_b[0], ak + roff_b[0], aq + TQ + roff_b[0], ak + TK + roff_b[0]);
-#pragma unroll
-      for (int st = 0; st < NS; st += 2) {
-        rd4(q1, k1, d1, v1, aq + roff_b[st + 1], ak + roff_b[st + 1], aq + TQ + roff_b[st + 1], ak + TK + roff_b[st + 1]);
-        tie4<4>(q0, k0, d0, v0);
-        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(frag8, q0), __builtin_bit_cast(frag8, k0), sacc, 0, 0, 0);
-        pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(frag8, d0), __builtin_bit_cast(frag8, v0), pacc, 0, 0, 0);
-        if (st + 2 < NS) {
-          rd4(q0, k0, d0, v0, aq + roff_b[st + 2], ak + roff_b[st + 2], aq + TQ + roff_b[st + 2], ak + TK + roff_b[st + 2]);
-          tie4<4>(q1, k1, d1, v1);
-        } else {
-          tie4<0>(q1, k1, d1, v1);
-        }
-        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(frag8, q1), __builtin_bit_cast(frag8, k1), sacc, 0, 0, 0);
-        pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(frag8, d1), __builtin_bit_cast(frag8, v1), pacc, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // query qq is live for this lane's key iff qlo <= qq < qlim: one unsigned compare per element
-    const int qoff = qt * QT + 32 * u + 4 * hf - qlo;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const f32x4 l4 = *reinterpret_cast<const f32x4*>(slse + 32 * u + 8 * rr + 4 * hf);
-      const f32x4 d4 = *reinterpret_cast<const f32x4*>(sdel + 32 * u + 8 * rr + 4 * hf);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = rr * 4 + j;
-        float pv = fast_exp2(fmaf(sacc[r], c, -l4[j]));  // lse staged as lse * log2(e)
-        if ((unsigned)(qoff + 8 * rr + j) >= qspan) pv = 0.f;
-        sacc[r] = pv;
-        pacc[r] = pv * (pacc[r] - d4[j]);
-      }
-    }
-    // dV += P^T dO ; dK += dS^T Q over this wave's 32 query rows
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const frag8 pf = pack_frag(sacc, s);
-      const frag8 df = pack_frag(pacc, s);
-      if (DS_OUT) {
-        // dS^T[key][q] (the bf16 operand of dK) for the dQ kernel: registers 8s..8s+3 / 8s+4..8s+7
-        // are query rows 16s + 4hf + 0..3 / 16s + 8 + 4hf + 0..3 of this wave's 32
-        const u16x8 w = __builtin_bit_cast(u16x8, df);
-        // (128-query block (qt QT) / 128 at st_blk)
-        u16* row = dST + ((int64_t)b * H + h) * st_bh + (int64_t)((qt * QT) >> 7) * st_blk + (int64_t)key * ldst +
-                   ((qt * QT) & 127) + 32 * u + 16 * s + 4 * hf;
-        *reinterpret_cast<u16x4*>(row) = u16x4{w[0], w[1], w[2], w[3]};
-        *reinterpret_cast<u16x4*>(row + 8) = u16x4{w[4], w[5], w[6], w[7]};
-      }
-      {
-        // transposed dO / Q fragments by inline asm, one column block ahead of the MFMAs
-        const unsigned kb = lds_addr(buf) + 2u * D * (32u * u + 16u * s);
-        s16x4 dl0, dh0, ql0, qh0, dl1, dh1, ql1, qh1;
-        __builtin_amdgcn_sched_barrier(0);
-        rd4t(dl0, dh0, ql0, qh0, kb + TQ + toff_b[0][0], kb + TQ + toff_b[0][1], kb + toff_b[0][0], kb + toff_b[0][1]);
-#pragma unroll
-        for (int dt = 0; dt < ND; dt += 2) {
-          rd4t(dl1, dh1, ql1, qh1, kb + TQ + toff_b[dt + 1][0], kb + TQ + toff_b[dt + 1][1], kb + toff_b[dt + 1][0],
-               kb + toff_b[dt + 1][1]);
-          tie4t<4>(dl0, dh0, ql0, qh0);
-          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, tr_join(dl0, dh0), dv[dt], 0, 0, 0);
-          dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, tr_join(ql0, qh0), dk[dt], 0, 0, 0);
-          if (dt + 2 < ND) {
-            rd4t(dl0, dh0, ql0, qh0, kb + TQ + toff_b[dt + 2][0], kb + TQ + toff_b[dt + 2][1], kb + toff_b[dt + 2][0],
-                 kb + toff_b[dt + 2][1]);
-            tie4t<4>(dl1, dh1, ql1, qh1);
-          } else {
-            tie4t<0>(dl1, dh1, ql1, qh1);
-          }
-          dv[dt + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, tr_join(dl1, dh1), dv[dt + 1], 0, 0, 0);
-          dk[dt + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, tr_join(ql1, qh1), dk[dt + 1], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (more) store_aux(nbuf);
-    // the next tile's DMA landed (MFMAs kept in front of the wait)
-    __builtin_amdgcn_sched_barrier(0);
-    // DS_OUT: the tile's four dS^T stores (two 8-B stores per 16-query slice, after the DMA in
-    // issue order) may stay in flight
-    if constexpr (DS_OUT) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  // pair reduction: half 1 parks its partial sums in LDS, half 0 adds them and stores
-  float* red = (float*)smem;  // [2 (dk, dv)][4 slices][ND][16][64] f32
-  auto slot = [&](int which, int dt, int r) { return red + ((((which * 4 + ksl) * ND + dt) * 16 + r) * 64 + lane); };
-  __syncthreads();
-  if (u == 1) {
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { *slot(0, dt, r) = dk[dt][r]; *slot(1, dt, r) = dv[dt][r]; }
-  }
-  __syncthreads();
-  if (u == 0) {
-    // wave-uniform row base (scalar), one 32-bit lane offset (4 hf rows + column lane & 31);
-    // row r's offset acc_row(r, 0) * ld is scalar too, the column block dt * 32 an immediate:
-    // one saddr store per element instead of 64-bit address arithmetic per element
-    const int k0 = kb * KB + ksl * 32;
-    u16* dKr = dK + ((int64_t)b * Lk + k0) * lddk + (int64_t)h * D;
-    u16* dVr = dV + ((int64_t)b * Lk + k0) * lddv + (int64_t)h * D;
-    const unsigned lk = (unsigned)(4 * hf * lddk + (lane & 31)) * 2u, lv = (unsigned)(4 * hf * lddv + (lane & 31)) * 2u;
-    const int left = Lk - k0;  // rows of this slice that exist (>= 32 on all but the last block)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      if (acc_row(r, hf) < left) {
-        u16* pk = dKr + (int64_t)acc_row(r, 0) * lddk;
-        u16* pv = dVr + (int64_t)acc_row(r, 0) * lddv;
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) {
-          *(u16*)((char*)pk + (lk + dt * 64u)) = f2bf((dk[dt][r] + *slot(0, dt, r)) * scale);
-          *(u16*)((char*)pv + (lv + dt * 64u)) = f2bf(dv[dt][r] + *slot(1, dt, r));
-        }
-      }
-    }
-  }
+  using SEQ = const int32_t*;
+#include "attn_bwd_dkdv8_body.h"
+}
+// packed sequences (cullavo_attn_bwd_varlen): causal, rows and lengths from the VarSeq
+template <int D, bool DS_OUT>
+__global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_varlen_k(
+    const u16* __restrict__ Q, int64_t ldq, const u16* __restrict__ K, int64_t ldk,
+    const u16* __restrict__ V, int64_t ldv, const u16* __restrict__ dO, int64_t lddo,
+    const float* __restrict__ LSE, const float* __restrict__ DELTA, u16* __restrict__ dK,
+    int64_t lddk, u16* __restrict__ dV, int64_t lddv, int H, float scale, VarSeq kv_start,
+    u16* __restrict__ dST, int64_t ldst, int64_t st_bh, int64_t st_blk) {
+  using SEQ = VarSeq;
+  constexpr bool CAUSAL = true;
+  const int LqG = kv_start.max_len, LkG = LqG;
+#include "attn_bwd_dkdv8_body.h"
 }
 
 // ============================================================================================
@@ -1223,26 +1088,28 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_k(
 // K and dS^T tiles are staged through registers (StageT): the LDS-DMA and 4-stage ring forms of
 // round 6 moved nothing (130.2 / 129.6 / 130.4 / 131.4 us, profiles/r06/attn/README_r06.txt; the
 // ring kernel lives on in tools/lab/dq_ring.inc).
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, class SEQ = const int32_t*>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_ds_k(const u16* __restrict__ K, int64_t ldk,
                                                            const u16* __restrict__ dST, int64_t ldst, int64_t st_bh, int64_t st_blk,
                                                            int LkP, u16* __restrict__ dQ, int64_t lddq, int H,
-                                                           int Lq, int Lk, float scale,
-                                                           const int32_t* __restrict__ kv_start) {
+                                                           int LqG, int LkG, float scale,
+                                                           typename SeqArg<SEQ>::type kv_start) {
   constexpr int KT = 64, QB = 128;
   constexpr int TK = KT * D * 2, TS = KT * QB * 2, BUF = TK + TS;
   constexpr int NS = KT / 16, ND = D / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  const int nqb = (Lq + QB - 1) / QB;
+  const int nqb = (seq_grid_rows(kv_start, LqG) + QB - 1) / QB;
   const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int qi = lid % nqb, hb = lid / nqb;
   const int qb = CAUSAL ? (nqb - 1 - qi) : qi;
   const int h = hb % H, b = hb / H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hf = lane >> 5;
   const int q = qb * QB + wave * 32 + (lane & 31);
-  const int kstart = kv_start ? kv_start[b] : 0;
-  const u16* Kb = K + (int64_t)b * Lk * ldk + (int64_t)h * D;
+  const int kstart = seq_kstart(kv_start, b);
+  const int Lq = seq_rows(kv_start, b, LqG), Lk = seq_rows(kv_start, b, LkG);  // this sequence's rows
+  if constexpr (kVarlen<SEQ>) if (qb * QB >= Lq) return;  // a tile past the sequence's end (workgroup-uniform)
+  const u16* Kb = K + seq_row0(kv_start, b, LkG) * ldk + (int64_t)h * D;
   const u16* Sb = dST + ((int64_t)b * H + h) * st_bh + qb * st_blk;
 
   f32x16 dq[ND];
@@ -1287,7 +1154,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_ds_k(const u16* __restrict
     __syncthreads();
   }
   if (q < Lq) {
-    u16* dQb = dQ + ((int64_t)b * Lq + q) * lddq + (int64_t)h * D;
+    u16* dQb = dQ + (seq_row0(kv_start, b, LqG) + q) * lddq + (int64_t)h * D;
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
@@ -1360,6 +1227,22 @@ int fwd_ragged_launch(const u16* q, int64_t ldq, const u16* kc, const u16* vc, i
   return cullavo_check_launch("attn_fwd_ragged");
 }
 
+template <int D>
+int fwd_varlen_launch(const u16* q, int64_t ldq, const u16* k, int64_t ldk, const u16* v, int64_t ldv, u16* o,
+                      int64_t ldo, float* lse, int B, int H, int max_len, float scale, const int32_t* seq_start,
+                      const int32_t* seq_len, hipStream_t s) {
+  const int smem = 4 * 64 * D * 2;
+  static bool once = false;
+  if (!once) {
+    set_smem(attn_fwd_varlen_k<D>, smem);
+    once = true;
+  }
+  const unsigned grid = (unsigned)(cdiv(max_len, 128) * H * B);
+  attn_fwd_varlen_k<D><<<grid, 256, smem, s>>>(q, ldq, k, ldk, v, ldv, o, ldo, lse, H, max_len, scale, seq_start,
+                                               seq_len);
+  return cullavo_check_launch("attn_fwd_varlen");
+}
+
 // backward mode (cullavo_attn_set_bwd_tiles):
 //   0 = the 4-wave kernels, 32-row dK/dV tiles and 32-key dQ tiles (the plain pair);
 //   2 = as 0 with 64-key dQ tiles, bitwise equal to 0;
@@ -1370,12 +1253,13 @@ int fwd_ragged_launch(const u16* q, int64_t ldq, const u16* kc, const u16* vc, i
 // The 64-row dK/dV tiles (modes 1, 3) lost the tile sweep on both head dims and left with ABI 6.
 int g_bwd_tiles = -1;
 
-// delta, then the mode's dK/dV kernel, then its dQ kernel (ds: the dS^T workspace of mode 7)
-template <int D, bool CAUSAL>
+// delta, then the mode's dK/dV kernel, then its dQ kernel (ds: the dS^T workspace of mode 7). ks:
+// kv_start of the uniform grid, or the VarSeq of packed sequences (Lq = Lk = its max_len)
+template <int D, bool CAUSAL, class SEQ>
 int bwd_launch(const u16* q, int64_t ldq, const u16* k, int64_t ldk, const u16* v, int64_t ldv, const u16* o,
                int64_t ldo, const u16* dout, int64_t lddo, const float* lse, float* delta, u16* dq, int64_t lddq,
                u16* dk, int64_t lddk, u16* dv, int64_t lddv, int B, int H, int Lq, int Lk, float scale,
-               const int32_t* ks, int mode, u16* ds, hipStream_t s) {
+               SEQ ks, int mode, u16* ds, hipStream_t s) {
   // 4-wave dK/dV: 2 x [Q | dO | lse | delta] tiles of 32 rows
   const int smem_a4 = 2 * (2 * 32 * D * 2 + 2 * 32 * 4);
   // 8-wave dK/dV: K, V images (2 x 128 x D) + 2 x [Q | dO | lse | delta] tiles of 64 rows; the pair
@@ -1385,38 +1269,59 @@ int bwd_launch(const u16* q, int64_t ldq, const u16* k, int64_t ldk, const u16* 
   const int smem_qds = 2 * (64 * D * 2 + 64 * 128 * 2);            // dQ from dS^T: 2 x [K | dS^T] tiles
   static bool once = false;
   if (!once) {
-    set_smem(attn_bwd_dkdv_k<D, CAUSAL>, smem_a4);
-    set_smem(attn_bwd_dkdv8_k<D, CAUSAL, false>, smem_a8);
-    set_smem(attn_bwd_dkdv8_k<D, CAUSAL, true>, smem_a8);
-    set_smem(attn_bwd_dq_k<D, CAUSAL, 32>, smem_q32);
-    set_smem(attn_bwd_dq_k<D, CAUSAL, 64>, smem_q64);
-    set_smem(attn_bwd_dq_ds_k<D, CAUSAL>, smem_qds);
+    set_smem(attn_bwd_dkdv_k<D, CAUSAL, SEQ>, smem_a4);
+    if constexpr (kVarlen<SEQ>) {
+      set_smem(attn_bwd_dkdv8_varlen_k<D, false>, smem_a8);
+      set_smem(attn_bwd_dkdv8_varlen_k<D, true>, smem_a8);
+    } else {
+      set_smem(attn_bwd_dkdv8_k<D, CAUSAL, false>, smem_a8);
+      set_smem(attn_bwd_dkdv8_k<D, CAUSAL, true>, smem_a8);
+    }
+    set_smem(attn_bwd_dq_k<D, CAUSAL, 32, SEQ>, smem_q32);
+    set_smem(attn_bwd_dq_k<D, CAUSAL, 64, SEQ>, smem_q64);
+    set_smem(attn_bwd_dq_ds_k<D, CAUSAL, SEQ>, smem_qds);
     once = true;
   }
   const int64_t rows = (int64_t)B * Lq * H;
-  attn_delta_k<D><<<(unsigned)cdiv(rows * (D / 8), 256), 256, 0, s>>>(o, ldo, dout, lddo, delta, B, H, Lq);
+  if constexpr (kVarlen<SEQ>)
+    attn_delta_k<D, VarSeq><<<(unsigned)cdiv(rows * (D / 8), 256), 256, 0, s>>>(o, ldo, dout, lddo, delta, B, H, ks);
+  else
+    attn_delta_k<D><<<(unsigned)cdiv(rows * (D / 8), 256), 256, 0, s>>>(o, ldo, dout, lddo, delta, B, H, Lq);
   const unsigned gk = (unsigned)(cdiv(Lk, 128) * H * B), gq = (unsigned)(cdiv(Lq, 128) * H * B);
   // the dS^T workspace is row-major: LkP key rows of LqP queries, 128-query block qb at column 128 qb
   const int64_t LkP = ds_rows(Lk), LqP = ds_cols(Lq);
-  if (mode == 7)
-    attn_bwd_dkdv8_k<D, CAUSAL, true><<<gk, 512, smem_a8, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk,
-                                                             dv, lddv, H, Lq, Lk, scale, ks, ds, LqP, LkP * LqP, 128);
-  else if (mode == 4)
-    attn_bwd_dkdv8_k<D, CAUSAL, false><<<gk, 512, smem_a8, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk,
-                                                              dv, lddv, H, Lq, Lk, scale, ks, nullptr, 0, 0, 0);
-  else
-    attn_bwd_dkdv_k<D, CAUSAL><<<gk, 256, smem_a4, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk, dv,
+  if (mode == 7 || mode == 4) {
+    u16* st = mode == 7 ? ds : nullptr;
+    const int64_t ldst = mode == 7 ? LqP : 0, st_bh = mode == 7 ? LkP * LqP : 0, st_blk = mode == 7 ? 128 : 0;
+    if constexpr (kVarlen<SEQ>) {
+      static_assert(CAUSAL, "packed sequences are causal");
+      if (mode == 7)
+        attn_bwd_dkdv8_varlen_k<D, true><<<gk, 512, smem_a8, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk,
+                                                                 dv, lddv, H, scale, ks, st, ldst, st_bh, st_blk);
+      else
+        attn_bwd_dkdv8_varlen_k<D, false><<<gk, 512, smem_a8, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk,
+                                                                  dv, lddv, H, scale, ks, st, ldst, st_bh, st_blk);
+    } else {
+      if (mode == 7)
+        attn_bwd_dkdv8_k<D, CAUSAL, true><<<gk, 512, smem_a8, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk,
+                                                                  dv, lddv, H, Lq, Lk, scale, ks, st, ldst, st_bh, st_blk);
+      else
+        attn_bwd_dkdv8_k<D, CAUSAL, false><<<gk, 512, smem_a8, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk,
+                                                                   dv, lddv, H, Lq, Lk, scale, ks, st, ldst, st_bh, st_blk);
+    }
+  } else
+    attn_bwd_dkdv_k<D, CAUSAL, SEQ><<<gk, 256, smem_a4, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dk, lddk, dv,
                                                       lddv, H, Lq, Lk, scale, ks);
   if (mode == 7)
-    attn_bwd_dq_ds_k<D, CAUSAL><<<gq, 256, smem_qds, s>>>(k, ldk, ds, LqP, LkP * LqP, 128, (int)LkP, dq, lddq, H, Lq, Lk,
+    attn_bwd_dq_ds_k<D, CAUSAL, SEQ><<<gq, 256, smem_qds, s>>>(k, ldk, ds, LqP, LkP * LqP, 128, (int)LkP, dq, lddq, H, Lq, Lk,
                                                         scale, ks);
   else if (mode == 2)
-    attn_bwd_dq_k<D, CAUSAL, 64><<<gq, 256, smem_q64, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq, lddq, H,
+    attn_bwd_dq_k<D, CAUSAL, 64, SEQ><<<gq, 256, smem_q64, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq, lddq, H,
                                                          Lq, Lk, scale, ks);
   else
-    attn_bwd_dq_k<D, CAUSAL, 32><<<gq, 256, smem_q32, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq, lddq, H,
+    attn_bwd_dq_k<D, CAUSAL, 32, SEQ><<<gq, 256, smem_q32, s>>>(q, ldq, k, ldk, v, ldv, dout, lddo, lse, delta, dq, lddq, H,
                                                          Lq, Lk, scale, ks);
-  return cullavo_check_launch("attn_bwd");
+  return cullavo_check_launch(kVarlen<SEQ> ? "attn_bwd_varlen" : "attn_bwd");
 }
 
 }  // namespace
@@ -1576,7 +1481,7 @@ extern "C" int cullavo_attn_bwd_ws(const void* q, int64_t ldq, const void* k, in
   u16* ds = (u16*)workspace;
   if (mode == 7 && (ds == nullptr || workspace_bytes < cullavo_attn_bwd_workspace(B, H, Lq, Lk, D, dtype))) mode = 4;
   auto run = [&](auto d_c, auto causal_c) {
-    return bwd_launch<decltype(d_c)::value, decltype(causal_c)::value>(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse,
+    return bwd_launch<decltype(d_c)::value, decltype(causal_c)::value, const int32_t*>(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse,
                                                                        delta, dQ, lddq, dK, lddk, dV, lddv, B, H, Lq,
                                                                        Lk, scale, kv_start, mode, ds, s);
   };
@@ -1584,4 +1489,87 @@ extern "C" int cullavo_attn_bwd_ws(const void* q, int64_t ldq, const void* k, in
   using D64 = std::integral_constant<int, 64>;
   if (D == 128) return causal ? run(D128{}, std::true_type{}) : run(D128{}, std::false_type{});
   return causal ? run(D64{}, std::true_type{}) : run(D64{}, std::false_type{});
+}
+
+// ---- packed sequences of unequal length (causal, bf16, D 64 / 128) -----------------------------
+// seq_start / seq_len are device values, so the host checks only what it holds. With
+// cullavo_attn_varlen_set_check(1) the entry points also read both arrays back (a stream
+// synchronisation per call: for tests and debugging, off by default) and refuse a length outside
+// [0, max_len] or a negative start before anything is launched.
+static int g_varlen_check = 0;
+
+extern "C" int cullavo_attn_varlen_set_check(int on) {
+  const int prev = g_varlen_check;
+  g_varlen_check = on != 0;
+  return prev;
+}
+
+static int varlen_check_device(const char* fn, const int32_t* seq_start, const int32_t* seq_len, int B, int max_len,
+                               hipStream_t s) {
+  std::vector<int32_t> host(2 * (size_t)B);
+  if (hipMemcpyAsync(host.data(), seq_start, B * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(host.data() + B, seq_len, B * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return cullavo_set_error(std::string(fn) + ": reading seq_start / seq_len back failed"), CULLAVO_EHIP;
+  for (int b = 0; b < B; ++b) {
+    if (host[B + b] < 0 || host[B + b] > max_len)
+      return cullavo_set_error(std::string(fn) + ": max_len is below a sequence's length (or a length is negative)"), CULLAVO_EINVAL;
+    if (host[b] < 0) return cullavo_set_error(std::string(fn) + ": a sequence start is negative"), CULLAVO_EINVAL;
+  }
+  return CULLAVO_OK;
+}
+
+#define ATTN_REQUIRE_VARLEN()                                                                                      \
+  CV_REQUIRE(dtype == CULLAVO_DT_BF16, CULLAVO_EUNSUPPORTED, "varlen attention: bf16 only");                       \
+  CV_REQUIRE(D == 64 || D == 128, CULLAVO_EUNSUPPORTED, "varlen attention: head_dim must be 64 or 128");           \
+  CV_REQUIRE(B >= 0 && H >= 0 && max_len >= 0, CULLAVO_EINVAL, "B, H and max_len must not be negative");           \
+  CV_REQUIRE(seq_start != nullptr && seq_len != nullptr, CULLAVO_EINVAL, "varlen attention: seq_start or seq_len is null")
+
+extern "C" int cullavo_attn_fwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                       int64_t ldv, void* o, int64_t ldo, float* lse, const int32_t* seq_start,
+                                       const int32_t* seq_len, int B, int H, int max_len, int D, float scale,
+                                       int dtype, void* stream) {
+  ATTN_REQUIRE_VARLEN();
+  ATTN_REQUIRE_STRIDES_X8(ldq, ldk, ldv, ldo);
+  ATTN_REQUIRE_STRIDES_HOLD_HD(ldq, ldk, ldv, ldo);
+  if (B == 0 || H == 0 || max_len == 0) return CULLAVO_OK;
+  hipStream_t s = CV_STREAM(stream);
+  if (g_varlen_check) {
+    const int rc = varlen_check_device(__func__, seq_start, seq_len, B, max_len, s);
+    if (rc != CULLAVO_OK) return rc;
+  }
+  const u16 *Q = (const u16*)q, *K = (const u16*)k, *V = (const u16*)v;
+  u16* O = (u16*)o;
+  if (D == 128) return fwd_varlen_launch<128>(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_len, scale, seq_start, seq_len, s);
+  return fwd_varlen_launch<64>(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_len, scale, seq_start, seq_len, s);
+}
+
+extern "C" int cullavo_attn_bwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                       int64_t ldv, const void* o, int64_t ldo, const void* dout, int64_t lddo,
+                                       const float* lse, float* delta, void* dq, int64_t lddq, void* dk,
+                                       int64_t lddk, void* dv, int64_t lddv, const int32_t* seq_start,
+                                       const int32_t* seq_len, int B, int H, int max_len, int D, float scale,
+                                       int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  ATTN_REQUIRE_VARLEN();
+  ATTN_REQUIRE_STRIDES_X8(ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv);
+  ATTN_REQUIRE_STRIDES_HOLD_HD(ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv);
+  if (B == 0 || H == 0 || max_len == 0) return CULLAVO_OK;
+  hipStream_t s = CV_STREAM(stream);
+  if (g_varlen_check) {
+    const int rc = varlen_check_device(__func__, seq_start, seq_len, B, max_len, s);
+    if (rc != CULLAVO_OK) return rc;
+  }
+  // as cullavo_attn_bwd_ws: mode 7 without its dS^T workspace runs the recompute path
+  int mode = bwd_mode(D);
+  u16* ds = (u16*)workspace;
+  if (mode == 7 && (ds == nullptr || workspace_bytes < cullavo_attn_bwd_workspace(B, H, max_len, max_len, D, dtype)))
+    mode = 4;
+  const VarSeq sq{seq_start, seq_len, max_len};
+  const u16 *Q = (const u16*)q, *K = (const u16*)k, *V = (const u16*)v, *O = (const u16*)o, *dO = (const u16*)dout;
+  u16 *dQ = (u16*)dq, *dK = (u16*)dk, *dV = (u16*)dv;
+  if (D == 128)
+    return bwd_launch<128, true, VarSeq>(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, delta, dQ, lddq, dK, lddk, dV,
+                                         lddv, B, H, max_len, max_len, scale, sq, mode, ds, s);
+  return bwd_launch<64, true, VarSeq>(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, delta, dQ, lddq, dK, lddk, dV,
+                                      lddv, B, H, max_len, max_len, scale, sq, mode, ds, s);
 }

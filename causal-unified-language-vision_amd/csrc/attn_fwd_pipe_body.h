@@ -20,13 +20,20 @@
 // holds some padding masks every key tile. past = Lk - Lq may be negative (a short cache behind a
 // long pad): queries below -past are padding by construction, kspan = 0 covers bad inputs. With
 // RAGGED = false, qpad is the constant 0 and every RAGGED term folds away.
+//
+// VARLEN (attn_fwd_varlen_k, CAUSAL = true, CACHED = RAGGED = false): sequences of unequal length
+// packed back to back. The kernel sets Lq = Lk = seq_len[b] and vl_row0 = seq_start[b] (workgroup-
+// uniform) before these statements; the grid and the lse rows are sized by vl_max, the host's upper
+// bound of the lengths. Only the base rows and the lse row stride differ from the uniform kernel, so
+// a sequence's workgroups run the statements of attn_fwd_pipe_k at B = 1, L = seq_len[b], bit for
+// bit. With VARLEN = false, vl_max and vl_row0 are constants and every VARLEN term folds away.
   constexpr int KT = 64;
   constexpr int TILE = KT * D * 2;
   constexpr int NS = D / 16;  // k-steps over D: 8 (D = 128) or 4 (D = 64)
   constexpr int ND = D / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K slots 0, 1 then V slots 0, 1
 
-  const int nqb = (Lq + 127) / 128;
+  const int nqb = ((VARLEN ? vl_max : Lq) + 127) / 128;
   const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int qi = lid % nqb, hb = lid / nqb;
   const int qb = CAUSAL ? (nqb - 1 - qi) : qi;
@@ -35,9 +42,9 @@
   const int q = qb * 128 + wave * 32 + (lane & 31);
   const int kstart = kv_start ? kv_start[b] : 0;
 
-  const u16* Qb = Q + (int64_t)b * Lq * ldq + (int64_t)h * D;
-  const u16* Kb = K + (CACHED ? (int64_t)b * ldv : (int64_t)b * Lk * ldk) + (int64_t)h * D;
-  const u16* Vb = V + (int64_t)b * (CACHED ? 1 : Lk) * ldv + (int64_t)h * D;
+  const u16* Qb = Q + (VARLEN ? vl_row0 : (int64_t)b * Lq) * ldq + (int64_t)h * D;
+  const u16* Kb = K + (CACHED ? (int64_t)b * ldv : (VARLEN ? vl_row0 : (int64_t)b * Lk) * ldk) + (int64_t)h * D;
+  const u16* Vb = V + (VARLEN ? vl_row0 : (int64_t)b * (CACHED ? 1 : Lk)) * ldv + (int64_t)h * D;
   const int64_t ldvt = CACHED ? ldk : ldv;  // V's token stride
   const int past = CACHED ? Lk - Lq : 0;
 
@@ -341,7 +348,7 @@
   // lane and its partner hold the same query row, so the row guard is uniform across the pair).
   {
     const float inv = l > 0.f ? 1.f / l : 0.f;
-    u16* Ob = O + ((int64_t)b * Lq + q) * ldo + (int64_t)h * D;
+    u16* Ob = O + ((VARLEN ? vl_row0 : (int64_t)b * Lq) + q) * ldo + (int64_t)h * D;
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
@@ -362,5 +369,5 @@
         }
       }
     if ((!CACHED || LSE != nullptr) && q < Lq && hf == 0)  // the cached entry point's lse is optional
-      LSE[((int64_t)b * H + h) * Lq + q] = l > 0.f ? (m + log2f(l)) * kLn2 : INFINITY;
+      LSE[((int64_t)b * H + h) * (VARLEN ? vl_max : Lq) + q] = l > 0.f ? (m + log2f(l)) * kLn2 : INFINITY;
   }

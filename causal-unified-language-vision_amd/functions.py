@@ -187,10 +187,16 @@ class StepContext:
     torch.manual_seed makes runs repeatable; backward reuses it to regenerate the masks).
     tail_layer / tail_rows: the supervised-row tail (ops.supervised_rows): the decoder layer that runs
     its MLP half on the rows tail_rows only and returns the compact [n, d] hidden state (the last layer,
-    set by the caller together with HeadLossRowsFn; None: every layer runs at full height)."""
+    set by the caller together with HeadLossRowsFn; None: every layer runs at full height).
+    packed: a packed.PackedPlan when h holds only the attended rows, sequence by sequence ([Tp, d],
+    CuLLaVOModel.packed_rows): the layers then run the varlen attention over plan.seq_start /
+    plan.seq_len instead of the [B, L] grid; position_ids are the packed rows' (no kv_start: nothing
+    padded is left). Everything else in a layer is row-wise. The LoRA dropout masks are keyed by the row
+    index the layer sees, which is then the packed row."""
 
     def __init__(self, B: int, L: int, position_ids, kv_start=None, lora_seed: int | None = None):
         self.tail_layer, self.tail_rows = None, None
+        self.packed = None
         self.B, self.L = B, L
         self.position_ids = position_ids.reshape(-1).contiguous()
         self.kv_start = kv_start
@@ -212,8 +218,15 @@ class LlamaLayerFn(torch.autograd.Function):
         qkv = ops.linear(x1, layer.w_qkv(), addend=t)  # [T, 3d]: q | k | v
         q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
         ops.rope(q, k, sctx.position_ids, hq=H, hk=H, head_dim=D, theta=cfg.rope_theta)
-        o, lse = ops.attn_fwd(q, k, v, B=sctx.B, H=H, Lq=sctx.L, Lk=sctx.L, D=D, scale=D ** -0.5, causal=True,
-                              kv_start=sctx.kv_start)
+        pk = sctx.packed
+        if pk is not None:
+            o = torch.empty((T, d), dtype=h.dtype, device=h.device)
+            o[pk.T:].zero_()  # the padding rows belong to no sequence: the kernels leave them alone
+            o, lse = ops.attn_fwd_varlen(q, k, v, pk.seq_start, pk.seq_len, B=sctx.B, H=H, max_len=pk.max_len, D=D,
+                                         scale=D ** -0.5, out=o)
+        else:
+            o, lse = ops.attn_fwd(q, k, v, B=sctx.B, H=H, Lq=sctx.L, Lk=sctx.L, D=D, scale=D ** -0.5, causal=True,
+                                  kv_start=sctx.kv_start)
         t, u_o = lg["o"].forward(o, tr, seed)
         h2 = ops.linear(o, layer.self_attn.o_proj.weight, residual=h, addend=t)
         # supervised-row tail: the MLP half of this layer feeds only the head, which reads the rows
@@ -289,8 +302,14 @@ class LlamaLayerFn(torch.autograd.Function):
         _write_dw(dh2, o, layer.self_attn.o_proj.weight)
         dqkv = torch.empty_like(qkv)
         q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-        ops.attn_bwd(q, k, v, o, do, lse, B=sctx.B, H=H, Lq=sctx.L, Lk=sctx.L, D=D, scale=D ** -0.5, causal=True,
-                     kv_start=sctx.kv_start, dq=dqkv[:, :d], dk=dqkv[:, d:2 * d], dv=dqkv[:, 2 * d:])
+        pk = sctx.packed
+        if pk is not None:
+            dqkv[pk.T:].zero_()
+            ops.attn_bwd_varlen(q, k, v, o, do, lse, pk.seq_start, pk.seq_len, B=sctx.B, H=H, max_len=pk.max_len, D=D,
+                                scale=D ** -0.5, dq=dqkv[:, :d], dk=dqkv[:, d:2 * d], dv=dqkv[:, 2 * d:])
+        else:
+            ops.attn_bwd(q, k, v, o, do, lse, B=sctx.B, H=H, Lq=sctx.L, Lk=sctx.L, D=D, scale=D ** -0.5, causal=True,
+                         kv_start=sctx.kv_start, dq=dqkv[:, :d], dk=dqkv[:, d:2 * d], dv=dqkv[:, 2 * d:])
         del do
         ops.rope(dqkv[:, :d], dqkv[:, d:2 * d], sctx.position_ids, hq=H, hk=H, head_dim=D, theta=cfg.rope_theta,
                  inverse=True)
@@ -465,6 +484,33 @@ class MergeFn(torch.autograd.Function):
         dtext = ops.row_gather2(text_dst.reshape(-1), dout, None).view(ts) if ctx.needs_input_grad[0] else None
         dimg = ops.row_gather2(img_dst, dout, None).view(ims) if ctx.needs_input_grad[1] else None
         return dtext, dimg, None, None, None
+
+
+class PackRowsFn(torch.autograd.Function):
+    """the rows x[rows] (rows: packed.PackedPlan.rows, -1 = a zero row); backward scatters into a
+    zero-filled tensor of x's height."""
+
+    @staticmethod
+    def forward(ctx, x, rows):
+        ctx.rows, ctx.full = rows, x.shape[0]
+        return ops.row_gather2(rows, x.contiguous(), None)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.rows_scatter(dy.contiguous(), ctx.rows, ctx.full), None
+
+
+class UnpackRowsFn(torch.autograd.Function):
+    """PackRowsFn's inverse: [full, cols] with y's row i in row rows[i], zeros elsewhere."""
+
+    @staticmethod
+    def forward(ctx, y, rows, full: int):
+        ctx.rows = rows
+        return ops.rows_scatter(y.contiguous(), rows, full)
+
+    @staticmethod
+    def backward(ctx, dx):
+        return ops.row_gather2(ctx.rows, dx.contiguous(), None), None, None
 
 
 # ---------------------------------------------------------------------------------------------

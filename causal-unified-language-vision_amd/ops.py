@@ -705,6 +705,73 @@ def attn_bwd(q, k, v, o, do, lse, *, B: int, H: int, Lq: int, Lk: int, D: int, s
     return dq, dk, dv
 
 
+def _varlen_args(name: str, tensors, seq_start, seq_len, B: int, H: int, D: int, max_len: int):
+    """the shape / stride checks attn_fwd_varlen and attn_bwd_varlen share (device values are the
+    kernel's to clamp: see the header)"""
+    _int32_rows("seq_start", seq_start, B)
+    _int32_rows("seq_len", seq_len, B)
+    if max_len < 0:
+        raise ValueError(f"{name}: max_len {max_len} is negative")
+    # T is whatever the caller's buffers hold: which of their rows belong to a sequence is decided by the
+    # device values seq_start / seq_len, which the host does not read (keeping them inside T is the caller's)
+    T = tensors[0][1].shape[0]
+    for nm, t_ in tensors:
+        if t_.dim() != 2 or t_.stride(1) != 1 or t_.shape[1] != H * D or t_.shape[0] != T:
+            raise ValueError(f"{name}: {nm} must be a [{T}, {H * D}] row block with unit column stride, got "
+                             f"{tuple(t_.shape)} strides {t_.stride()}")
+        if t_.dtype != torch.bfloat16:
+            raise TypeError(f"{name}: {nm} is {t_.dtype}; the packed attention is bf16 only")
+    return T
+
+
+def attn_fwd_varlen(q, k, v, seq_start, seq_len, *, B: int, H: int, max_len: int, D: int, scale: float, out=None,
+                    lse=None):
+    """cullavo_attn_fwd_varlen: causal attention over B sequences of unequal length packed into the
+    rows of q / k / v, each a [T, H*D] view with any token stride that is a multiple of 8 (column blocks of
+    one q|k|v buffer, as the decoder layer holds them): sequence b owns rows seq_start[b] ..
+    seq_start[b] + seq_len[b] - 1 (int32 [B] on the device; gaps between sequences are legal and never
+    touched, seq_len[b] = 0 writes nothing). max_len: a host upper bound of seq_len. Returns
+    (o [T, H*D], lse [B, H, max_len] f32); rows of o outside every sequence and lse entries at or
+    beyond seq_len[b] are not written. Per sequence bitwise attn_fwd(B=1, L=seq_len[b], causal)."""
+    _dev(q, k, v, seq_start, seq_len, out, lse)
+    T = _varlen_args("attn_fwd_varlen", (("q", q), ("k", k), ("v", v)) + ((("out", out),) if out is not None else ()),
+                     seq_start, seq_len, B, H, D, max_len)
+    o = out if out is not None else torch.empty((T, H * D), dtype=q.dtype, device=q.device)
+    if lse is None:
+        lse = torch.empty((B, H, max_len), dtype=torch.float32, device=q.device)
+    elif lse.shape != (B, H, max_len) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError(f"attn_fwd_varlen: lse must be a contiguous f32 [{B}, {H}, {max_len}] tensor")
+    call("attn_fwd_varlen", _ptr(q), _ld(q), _ptr(k), _ld(k), _ptr(v), _ld(v), _ptr(o), _ld(o), _ptr(lse),
+         _ptr(seq_start), _ptr(seq_len), B, H, max_len, D, float(scale), _dt(q), _stream())
+    return o, lse
+
+
+def attn_bwd_varlen(q, k, v, o, do, lse, seq_start, seq_len, *, B: int, H: int, max_len: int, D: int, scale: float,
+                    dq=None, dk=None, dv=None, delta=None):
+    """cullavo_attn_bwd_varlen: the backward of attn_fwd_varlen (same packing; lse as it returned it,
+    [B, H, max_len]). dq / dk / dv default to new [T, H*D] tensors whose rows outside every sequence
+    are not written; delta (f32 [B, H, max_len], scratch) likewise. Returns (dq, dk, dv)."""
+    _dev(q, k, v, o, do, lse, seq_start, seq_len, dq, dk, dv, delta)
+    given = tuple((n, t_) for n, t_ in (("dq", dq), ("dk", dk), ("dv", dv)) if t_ is not None)
+    T = _varlen_args("attn_bwd_varlen", (("q", q), ("k", k), ("v", v), ("o", o), ("do", do)) + given, seq_start,
+                     seq_len, B, H, D, max_len)
+    if lse.shape != (B, H, max_len) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError(f"attn_bwd_varlen: lse must be a contiguous f32 [{B}, {H}, {max_len}] tensor")
+    if delta is None:
+        delta = torch.empty((B, H, max_len), dtype=torch.float32, device=q.device)
+    elif delta.shape != (B, H, max_len) or delta.dtype != torch.float32 or not delta.is_contiguous():
+        raise ValueError(f"attn_bwd_varlen: delta must be a contiguous f32 [{B}, {H}, {max_len}] tensor")
+    dq = dq if dq is not None else torch.empty((T, H * D), dtype=q.dtype, device=q.device)
+    dk = dk if dk is not None else torch.empty((T, H * D), dtype=q.dtype, device=q.device)
+    dv = dv if dv is not None else torch.empty((T, H * D), dtype=q.dtype, device=q.device)
+    nbytes = lib().cullavo_attn_bwd_workspace(B, H, max_len, max_len, D, _dt(q))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+    call("attn_bwd_varlen", _ptr(q), _ld(q), _ptr(k), _ld(k), _ptr(v), _ld(v), _ptr(o), _ld(o), _ptr(do), _ld(do),
+         _ptr(lse), _ptr(delta), _ptr(dq), _ld(dq), _ptr(dk), _ld(dk), _ptr(dv), _ld(dv), _ptr(seq_start),
+         _ptr(seq_len), B, H, max_len, D, float(scale), _dt(q), _ptr(ws), nbytes, _stream())
+    return dq, dk, dv
+
+
 # ---- token sampling (csrc/sample.hip) ----------------------------------------------------------
 def sample_token(logits, *, next_ids, step, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
                  do_sample: bool = True, seed: int = 0, row_offset=None, eos_id: int | None = None, pad_id: int = 0,

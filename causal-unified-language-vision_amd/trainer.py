@@ -129,6 +129,9 @@ class DefaultTrainer:
         # (batches that carry num_supervised). CULLAVO_SUPERVISED_ROWS=0 keeps the full path for A/B.
         cm = self.model.cullavo_model if hasattr(self.model, "cullavo_model") else self.model
         cm.supervised_rows = os.environ.get("CULLAVO_SUPERVISED_ROWS", "1") != "0"
+        # opt-in: batches with padding run only their attended rows through the decoder layers
+        # (CuLLaVOModel.packed_rows; text-only batches carry attended_lens). Off by default.
+        cm.packed_rows = os.environ.get("CULLAVO_PACKED_ROWS", "0") == "1"
         self.train_dataloaders = self.pipeline.get_dataloaders(self, "train", is_evaluation=False)
         self.create_optimizer_and_scheduler()
         self._initialize_accelerator()

@@ -62,7 +62,8 @@ extern "C" {
    mode of cullavo_gemm_set_msplit). cullavo_sample_token
    was added under 8 without a bump, as cullavo_lora_dx was under its version: a pure addition that
    changes no existing signature; so were cullavo_attn_fwd_ragged and cullavo_kv_append_ragged under 9
-   (the ragged KV cache: two new entry points, nothing existing touched). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
+   (the ragged KV cache: two new entry points, nothing existing touched), and cullavo_attn_fwd_varlen,
+   cullavo_attn_bwd_varlen and cullavo_attn_varlen_set_check (packed training sequences). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
 #define CULLAVO_ABI_VERSION 9
 
 int cullavo_abi_version(void);
@@ -420,6 +421,40 @@ int cullavo_attn_fwd_ragged(const void* q, int64_t ldq, const void* k_cache, con
                             int64_t ld_tok, int64_t ld_batch, void* o, int64_t ldo, float* lse, int B,
                             int H, int Lq, const int32_t* kv_len, const int32_t* q_pad, int D, float scale,
                             const int32_t* kv_start, int dtype, void* stream);
+/* Packed sequences of unequal length (added under ABI 9, additive): the training step's causal
+ * attention over only the attended tokens, what the reference's FA2 path computes after unpadding
+ * (flash_attn_varlen_func). q, k, v, o and their gradients are [T, H*D] row blocks with a token
+ * stride, as in cullavo_attn_fwd / cullavo_attn_bwd_ws; sequence b owns rows seq_start[b] ..
+ * seq_start[b] + seq_len[b] - 1 and attends causally within them. seq_start and seq_len [B] are on
+ * the device; max_len is a host upper bound of seq_len that sizes the grids, lse and delta
+ * ([B, H, max_len], entries at or beyond seq_len[b] neither read nor written) and the dS^T workspace
+ * (cullavo_attn_bwd_workspace(B, H, max_len, max_len, D, dtype); without it the recompute path runs,
+ * as in cullavo_attn_bwd_ws). seq_len[b] == 0 is legal and writes nothing; rows between sequences
+ * are never read or written. Causal, bf16, D 64 or 128 only. The kernels are further instantiations
+ * of the uniform ones (the pipelined forward whatever cullavo_attn_set_stage says -- stage 4 is its
+ * bitwise twin -- and the backward kernels of the current cullavo_attn_set_bwd_tiles mode): for every
+ * b the results equal, bit for bit, cullavo_attn_fwd / cullavo_attn_bwd_ws at B = 1, L = seq_len[b],
+ * causal, on that sequence's rows alone.
+ * Errors (before any launch): dtype / D unsupported (CULLAVO_EUNSUPPORTED); seq_start or seq_len
+ * null, a negative B, H or max_len, a stride that is no multiple of 8 or smaller than H*D
+ * (CULLAVO_EINVAL). The values seq_start and seq_len point to cannot be validated without a
+ * read-back: the kernels clamp seq_len[b] to [0, max_len], so a bad length changes the result but
+ * indexes nothing outside sequence b's part of lse / delta / the workspace; seq_start[b] is the
+ * caller's to keep inside the buffers. cullavo_attn_varlen_set_check(1) makes both entry points read
+ * the two arrays back first (one stream synchronisation per call: for tests and debugging, off by
+ * default) and return CULLAVO_EINVAL when max_len is below a length, a length is negative or a start
+ * is negative. Returns the setting before the call. */
+int cullavo_attn_fwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                            int64_t ldv, void* o, int64_t ldo, float* lse, const int32_t* seq_start,
+                            const int32_t* seq_len, int B, int H, int max_len, int D, float scale,
+                            int dtype, void* stream);
+int cullavo_attn_bwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                            int64_t ldv, const void* o, int64_t ldo, const void* dout, int64_t lddo,
+                            const float* lse, float* delta, void* dq, int64_t lddq, void* dk,
+                            int64_t lddk, void* dv, int64_t lddv, const int32_t* seq_start,
+                            const int32_t* seq_len, int B, int H, int max_len, int D, float scale,
+                            int dtype, void* workspace, size_t workspace_bytes, void* stream);
+int cullavo_attn_varlen_set_check(int on);
 /* Decode-step Linear over M <= 16 rows (one token per sequence; reference: the cached forward's
  * decoder layer, cullavo/arch_cullavo.py:605-636) with its input transform fused into the weight
  * stream (csrc/gemv.hip): y[M,N] = X W^T (+ residual), W [N,K] bf16 (ldw), where X is
