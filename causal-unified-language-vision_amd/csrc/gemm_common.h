@@ -38,12 +38,12 @@ struct GemmArgs {
   int sk_dp;          // 8-wave kernels: tiles in the grid (the XCD remap's block count)
   int group_m;        // 8-wave tile order: > 0 groups of group_m M-tiles sweep N; < 0 groups of
                       // -group_m N-tiles sweep M
-  // fused LoRA up-projection (gemm256_k<..., LORA = true>): t = round(lora_scale * u_m B_m^T) for
+  // fused LoRA up-projection (gemm256_k / gemv_k / nf4_gemv_k <..., LORA = true>): t = round(lora_scale * u_m B_m^T) for
   // the module m = n / lora_out of each output column, added to round(alpha*acc + bias)
   const u16* lora_u;  // [M, n_mod * 64] (row stride ld_lu): lora_A outputs of the group's modules
   int64_t ld_lu;
   const u16* lora_b;  // [N, 64] row-major: the group's lora_B weights stacked in column order
-  int64_t lora_out;   // output columns per module (a multiple of 256)
+  int64_t lora_out;   // output columns per module (a multiple of 256; the decode products: of 16)
   float lora_scale;
 };
 
@@ -311,6 +311,53 @@ DEV void store4(const GemmArgs& p, const f32x4& acc, int64_t m, int64_t n) {
     }
     *reinterpret_cast<f32x4*>(cp) = o;
   }
+}
+
+// ---- the decode products' fused LoRA term (gemv.hip gemv_k, nf4.hip nf4_gemv_k; LORA = true) ----
+// For a workgroup's 16 weight rows and the M <= 16 decode rows, t[b][n] = bf16(scale * s),
+// s = sum_{j < 64} B[n][j] u[b][j] in f32, in the order of the K = 64 product that materialises the
+// term (LoraGroup.up_project -> gemv_k at K = 64): the 32-deep k-steps 0 and 1 are one MFMA each
+// from a zero accumulator (waves 0 and 1 of that launch), the partials are summed in wave order
+// with the other waves' zeros behind them, and store4 scales the sum by alpha = scale and rounds it.
+// Operands as gemv_k's: lora_B rows are the MFMA's A operand (lane: row lane & 15, k at
+// 8 (lane >> 4)), the u rows its B operand, so lane (r, g) ends with t of decode row r and the
+// tile's rows 4 g .. 4 g + 3 -- store4's layout in both kernels.
+// brow: this lane's lora_B row (64 bf16); urow: this lane's u row at its module's 64-column block,
+// nullptr for a lane whose decode row is past M (zeros, never read)
+DEV void lora_frags(const u16* brow, const u16* urow, int g, frag8 (&b)[2], frag8 (&u)[2]) {
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    b[ks] = __builtin_bit_cast(frag8, *reinterpret_cast<const u16x8*>(brow + 32 * ks + 8 * g));
+    u[ks] = urow ? __builtin_bit_cast(frag8, *reinterpret_cast<const u16x8*>(urow + 32 * ks + 8 * g)) : frag8{};
+  }
+}
+
+DEV f32x4 lora_term(const frag8 (&b)[2], const frag8 (&u)[2], float scale) {
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[0], u[0], z, 0, 0, 0);
+  const f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[1], u[1], z, 0, 0, 0);
+  f32x4 t;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) t[j] = round_bf(((s0[j] + s1[j]) + 0.f) * scale);  // + 0: the idle waves' partials
+  return t;
+}
+
+// store4's chain for a decode product (bf16, no bias / activation / beta) whose LoRA addend t is in
+// registers: y = bf16(bf16(bf16(alpha acc) + t) + residual)
+DEV void store4_lora(const GemmArgs& p, const f32x4& acc, const f32x4& t, int64_t m, int64_t n) {
+  if (m >= p.M || n >= p.N) return;
+  float v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = round_bf(acc[j] * p.alpha) + t[j];
+  if (p.residual) {
+    const u16x4 rv = *reinterpret_cast<const u16x4*>(p.residual + m * p.ldr + n);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = round_bf(v[j]) + bf2f(rv[j]);
+  }
+  u16x4 o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = f2bf(v[j]);
+  *reinterpret_cast<u16x4*>((u16*)p.C + m * p.ldc + n) = o;
 }
 
 // the same epilogue for 8 consecutive columns C[m][n .. n+7] with 16-B accesses (the

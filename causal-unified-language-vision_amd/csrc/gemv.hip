@@ -70,9 +70,17 @@ DEV frag8 gemv_xfrag(const GemvArgs& a, const u16* xp, int64_t off, int64_t k, c
 // g and u of one output: y = bf16(bf16(silu(g)) * u) with g, u first rounded to bf16 as the
 // unfused product stores them -- bitwise swiglu_fwd_k of that product, without its launch or the
 // [M, 2N] round trip.
-template <int CT, int ORDER, int RB, int XF, int NBW = kGemvBatch, int NW = kGemvWaves, int OT = 0>
+// LORA (cullavo_decode_linear_lora): the adapters' term t = bf16(scale u_m B_m^T) of the workgroup's 16
+// rows (module m = n0 / lora_out; lora_out % 16 == 0, so one module per workgroup) computed by the
+// epilogue wave -- its 16 lora_B rows (128 B each) and the u rows are loaded ahead of the weight
+// stream, two MFMA k-steps (lora_term, gemm_common.h: the materialising product's order) run under
+// the first weight batch -- and added as store4 adds a materialised addend (store4_lora). OT 1: the
+// gate rows take module 0's u and lora_B rows, the up rows module 1's; g and u each become
+// bf16(bf16(acc) + t) before the SwiGLU, as the unfused product stores them. false: today's kernels.
+template <int CT, int ORDER, int RB, int XF, int NBW = kGemvBatch, int NW = kGemvWaves, int OT = 0, bool LORA = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NBW >= 16 ? 2 : (NBW >= 8 || XF == 1) ? 4 : 8))) void gemv_k(GemvArgs a) {
   static_assert(OT == 0 || RB == 1, "SwiGLU pairing: one 16-row block per workgroup");
+  static_assert(!LORA || (RB == 1 && CT == CULLAVO_DT_BF16), "LoRA term: bf16, one 16-row block per workgroup");
   const GemmArgs& p = a.g;
   __shared__ f32x4 red[NW][RB][64];
   const int lane = threadIdx.x & 63;
@@ -121,6 +129,33 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NBW >= 
       wpre = *reinterpret_cast<const u16x8*>(a.xf_w + wcol);
     }
   }
+  // LORA: the epilogue wave's lora_B and u fragments (lu2: OT 1, module 1's u rows for the up rows) and
+  // the term they give. XF 0 (the default decode step) has them in flight ahead of the weight stream and
+  // computes the term under the first batch; the input transforms' kernels have no registers to hold
+  // them across the stream (they spilled), so there the epilogue wave fetches them after its K range.
+  constexpr bool LORA_EARLY = LORA && XF == 0;
+  frag8 lb[2], lu[2], lu2[2];
+  f32x4 lt = {0.f, 0.f, 0.f, 0.f};
+  auto lora_load = [&]() {
+    const int64_t brow = OT == 1 ? min(n0 + (r & 7), p.N - 1) + (r >= 8 ? p.N : 0) : min(n0 + r, p.N - 1);
+    const u16* up = xrow ? p.lora_u + r * p.ld_lu + (OT == 1 ? 0 : (n0 / p.lora_out) * 64) : nullptr;
+    lora_frags(p.lora_b + brow * 64, up, g, lb, lu);
+    if constexpr (OT == 1) {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+        lu2[ks] = xrow ? __builtin_bit_cast(frag8, *reinterpret_cast<const u16x8*>(up + 64 + 32 * ks + 8 * g)) : frag8{};
+    }
+  };
+  auto lora_compute = [&]() {
+    lt = lora_term(lb, lu, p.lora_scale);
+    if constexpr (OT == 1) {
+      const f32x4 t2 = lora_term(lb, lu2, p.lora_scale);
+      if (g >= 2) lt = t2;  // lanes 32-63 hold the up rows
+    }
+  };
+  if constexpr (LORA_EARLY) {
+    if (wave == 0) lora_load();
+  }
   for (int64_t j0 = 0; j0 < per; j0 += NB) {
     frag8 w[NB][RB], x[NB];
 #pragma unroll
@@ -133,6 +168,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NBW >= 
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb)
         w[i][rb] = in ? __builtin_bit_cast(frag8, *reinterpret_cast<const u16x8*>(wrow[rb] + off)) : frag8{};
+    }
+    if constexpr (LORA_EARLY) {
+      if (wave == 0 && j0 == 0) lora_compute();  // under the first weight batch's latency
     }
     if (XF == 1 && j0 == 0) {
       // RMSNorm of the M rows, after the first batch of weight loads is in flight, by every thread of
@@ -198,6 +236,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NBW >= 
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[i][rb], x[i], acc[rb], 0, 0, 0);
   }
+  if constexpr (LORA && !LORA_EARLY) {
+    if (wave == 0) {
+      lora_load();
+      lora_compute();
+    }
+  }
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) red[wave][rb][lane] = acc[rb];
   __syncthreads();
@@ -207,6 +251,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NBW >= 
     for (int w2 = 1; w2 < NW; ++w2) s += red[w2][wave][lane];
     if constexpr (OT == 1) {
       // lanes 0-31 hold g of outputs n0 + 4 (lane >> 4) + j, lanes 32-63 the matching u
+      if constexpr (LORA) {  // g and u as the unfused product stores them with its addend
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = round_bf(round_bf(s[j]) + lt[j]);
+      }
       f32x4 u;
 #pragma unroll
       for (int j = 0; j < 4; ++j) u[j] = __shfl_xor(s[j], 32);
@@ -216,6 +264,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NBW >= 
         for (int j = 0; j < 4; ++j) o[j] = f2bf(round_bf(gemv_silu(round_bf(s[j]))) * round_bf(u[j]));
         *reinterpret_cast<u16x4*>(reinterpret_cast<u16*>(p.C) + r * p.ldc + n0 + 4 * g) = o;
       }
+    } else if constexpr (LORA) {
+      store4_lora(p, s, lt, r, n0 + 4 * g);
     } else {
       store4<CT>(p, s, r, n0 + 16 * wave + 4 * g);
     }
@@ -253,9 +303,40 @@ int cvgemm_launch_gemv(const cvgemm::GemmArgs& p, bool f32, hipStream_t s) {
   return cullavo_check_launch("gemv");
 }
 
-extern "C" int cullavo_decode_linear(int x_transform, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
-                                     const void* norm_w, float eps, const void* W, int64_t ldw, void* y,
-                                     int64_t ldy, const void* residual, int64_t ldr, void* stream) {
+// The decode products' LoRA arguments (cullavo_decode_linear_lora, cullavo_nf4_decode_linear_lora), checked
+// before any launch. rows: the weight's rows (N, or 2N with a SwiGLU output, where the group must be
+// exactly gate | up: two modules of N rows). Returns 0 and fills p's lora fields, or sets the error.
+int cvgemm_decode_lora_args(cvgemm::GemmArgs& p, const char* who, int64_t rows, bool swiglu_out, const void* lora_u,
+                            int64_t ld_lora_u, const void* lora_b, int64_t lora_out, int lora_r, float lora_scale) {
+  const std::string w(who);
+  if (lora_b == nullptr) {
+    cullavo_set_error(w + ": lora_u without lora_b");
+    return CULLAVO_EINVAL;
+  }
+  if (lora_r != 64 || lora_out <= 0 || lora_out % 16 != 0 || rows % lora_out != 0 || ld_lora_u % 8 != 0 ||
+      (swiglu_out && rows != 2 * lora_out)) {
+    cullavo_set_error(w + ": the fused LoRA term needs lora_r == 64, lora_out % 16 == 0, N == n_modules * lora_out "
+                          "(a SwiGLU output: the gate | up pair, two modules of N rows) and ld_lora_u % 8 == 0");
+    return CULLAVO_EUNSUPPORTED;
+  }
+  if (ld_lora_u < rows / lora_out * 64 || ((uintptr_t)lora_u & 15) != 0 || ((uintptr_t)lora_b & 15) != 0) {
+    cullavo_set_error(w + ": lora_u needs 64 columns per module (ld_lora_u >= n_modules * 64) and 16-byte aligned "
+                          "lora_u / lora_b");
+    return CULLAVO_EINVAL;
+  }
+  p.lora_u = (const u16*)lora_u;
+  p.ld_lu = ld_lora_u;
+  p.lora_b = (const u16*)lora_b;
+  p.lora_out = lora_out;
+  p.lora_scale = lora_scale;
+  return 0;
+}
+
+extern "C" int cullavo_decode_linear_lora(int x_transform, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
+                                          const void* norm_w, float eps, const void* W, int64_t ldw, void* y,
+                                          int64_t ldy, const void* residual, int64_t ldr, const void* lora_u,
+                                          int64_t ld_lora_u, const void* lora_b, int64_t lora_out, int lora_r,
+                                          float lora_scale, void* stream) {
   CV_REQUIRE(x_transform >= 0 && x_transform <= 4, CULLAVO_EINVAL, "decode_linear: transform 0 to 4");
   const int xf = (x_transform == 1 || x_transform == 4) ? 1 : x_transform == 2 ? 2 : 0;
   const bool ot = x_transform == 3 || x_transform == 4;
@@ -282,18 +363,35 @@ extern "C" int cullavo_decode_linear(int x_transform, int64_t M, int64_t N, int6
   p.act = CULLAVO_ACT_NONE;
   a.xf_w = (const u16*)norm_w;
   a.xf_eps = eps;
+  const int64_t wrows = ot ? 2 * N : N;
+  const bool lora = lora_u != nullptr;
+  if (lora) {
+    const int rc = cvgemm_decode_lora_args(p, "decode_linear_lora", wrows, ot, lora_u, ld_lora_u, lora_b, lora_out, lora_r,
+                                           lora_scale);
+    if (rc != 0) return rc;
+  }
   const unsigned grid = (unsigned)cdiv(N, ot ? 8 : 16);
   const size_t smem = xf == 1 ? (size_t)M * (K + 8) * 2 : 0;
   // the shapes' variants as cvgemm_launch_gemv picks them: 16 waves x 4-load batches for the widest
   // products, 4-load batches for K >= 8192, else 8-load batches (SwiGLU output: the 2N-row product)
-  const int64_t wrows = ot ? 2 * N : N;
   const int v = K >= 8192 ? 6 : wrows > 16384 ? 8 : kGemvDefault;
-#define DL(XF, OT)                                                                                            \
-  if (v == 8) gemv_k<CULLAVO_DT_BF16, 0, 1, XF, 4, 16, OT><<<grid, 64 * 16, smem, s>>>(a);                   \
-  else if (v == 6) gemv_k<CULLAVO_DT_BF16, 0, 1, XF, 4, kGemvWaves, OT><<<grid, 64 * kGemvWaves, smem, s>>>(a); \
-  else gemv_k<CULLAVO_DT_BF16, 0, 1, XF, 8, kGemvWaves, OT><<<grid, 64 * kGemvWaves, smem, s>>>(a);
+#define DLK(XF, OT, L)                                                                                              \
+  if (v == 8) gemv_k<CULLAVO_DT_BF16, 0, 1, XF, 4, 16, OT, L><<<grid, 64 * 16, smem, s>>>(a);                        \
+  else if (v == 6) gemv_k<CULLAVO_DT_BF16, 0, 1, XF, 4, kGemvWaves, OT, L><<<grid, 64 * kGemvWaves, smem, s>>>(a);   \
+  else gemv_k<CULLAVO_DT_BF16, 0, 1, XF, 8, kGemvWaves, OT, L><<<grid, 64 * kGemvWaves, smem, s>>>(a);
+#define DL(XF, OT) \
+  if (lora) { DLK(XF, OT, true) } else { DLK(XF, OT, false) }
   if (x_transform == 0) { DL(0, 0) } else if (x_transform == 1) { DL(1, 0) } else if (x_transform == 2) { DL(2, 0) }
   else if (x_transform == 3) { DL(0, 1) } else { DL(1, 1) }
 #undef DL
+#undef DLK
   return cullavo_check_launch("decode_linear");
 }
+
+extern "C" int cullavo_decode_linear(int x_transform, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
+                                     const void* norm_w, float eps, const void* W, int64_t ldw, void* y,
+                                     int64_t ldy, const void* residual, int64_t ldr, void* stream) {
+  return cullavo_decode_linear_lora(x_transform, M, N, K, x, ldx, norm_w, eps, W, ldw, y, ldy, residual, ldr, nullptr, 0,
+                                    nullptr, 0, 0, 0.f, stream);
+}
+

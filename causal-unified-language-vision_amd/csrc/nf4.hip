@@ -121,7 +121,13 @@ DEV unsigned nf4_pair(float a, float b) { return (unsigned)f2bf(a) | ((unsigned)
 // NW: waves per workgroup (K split NW ways, contiguous block ranges); NB: 64-blocks per load batch
 // and wave (NB x 512 B of codes in flight per wave); OT 1: SwiGLU of the product (gemv.hip OT 1: 8
 // gate rows and the matching 8 up rows of the fused [2N, K] weight per workgroup)
-template <int NW, int NB, int OT>
+// LORA (cullavo_nf4_decode_linear_lora): gemv.hip's fused LoRA term. Wave 0, which writes the tile,
+// loads its 16 lora_B rows and the u rows ahead of the code stream and runs the term's two MFMA
+// k-steps (lora_term, gemm_common.h) under the first batch; lora_B rows are that MFMA's A operand, so
+// lane (r, g) gets t of decode row r and weight rows 4 g .. 4 g + 3, the layout of the reduced tile.
+// OT 1: a second fragment set holds the up rows' lora_B (module 1) in tile rows 0-7, so the gate and
+// up terms of one output meet in one lane as the reduced g and u do. false: today's kernels.
+template <int NW, int NB, int OT, bool LORA = false>
 __global__ __launch_bounds__(64 * NW) void nf4_gemv_k(GemmArgs p, const uint8_t* __restrict__ codes,
                                                        const float* __restrict__ absmax) {
   __shared__ u32x2 table[256];  // code byte -> {hi pair, lo pair}; the even element (high nibble) first
@@ -143,6 +149,17 @@ __global__ __launch_bounds__(64 * NW) void nf4_gemv_k(GemmArgs p, const uint8_t*
   const float* arow = absmax + wr * nblk;
   const bool xrow = r < p.M;
   const u16* xp = p.A + (xrow ? r : 0) * p.lda + 16 * g;
+  // LORA: wave 0's lora_B and u fragments (OT 1: lb2 / lu2 the up rows' module), and the terms
+  frag8 lb[2], lu[2], lb2[2], lu2[2];
+  f32x4 lt = {0.f, 0.f, 0.f, 0.f}, lt2 = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (LORA) {
+    if (wave == 0) {
+      const int64_t brow = OT == 1 ? min(n0 + (r & 7), p.N - 1) : min(n0 + r, p.N - 1);
+      const u16* up = xrow ? p.lora_u + r * p.ld_lu + (OT == 1 ? 0 : (n0 / p.lora_out) * 64) : nullptr;
+      lora_frags(p.lora_b + brow * 64, up, g, lb, lu);
+      if constexpr (OT == 1) lora_frags(p.lora_b + (brow + p.N) * 64, xrow ? up + 64 : nullptr, g, lb2, lu2);
+    }
+  }
   __syncthreads();  // the table
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const int64_t b0 = wave * per, bend = min(nblk, b0 + per);
@@ -155,6 +172,12 @@ __global__ __launch_bounds__(64 * NW) void nf4_gemv_k(GemmArgs p, const uint8_t*
       const int64_t blk = in ? j0 + i : b0;
       w[i] = in ? __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(crow + blk * 32)) : u32x2{0u, 0u};
       am[i] = in ? arow[blk] : 0.f;
+    }
+    if constexpr (LORA) {
+      if (wave == 0 && j0 == 0) {  // the adapters' term, under the first code batch's latency
+        lt = lora_term(lb, lu, p.lora_scale);
+        if constexpr (OT == 1) lt2 = lora_term(lb2, lu2, p.lora_scale);
+      }
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
@@ -196,11 +219,20 @@ __global__ __launch_bounds__(64 * NW) void nf4_gemv_k(GemmArgs p, const uint8_t*
         f32x4 u = *reinterpret_cast<const f32x4*>(&red[0][r][8 + 4 * g]);
 #pragma unroll
         for (int w2 = 1; w2 < NW; ++w2) u += *reinterpret_cast<const f32x4*>(&red[w2][r][8 + 4 * g]);
+        if constexpr (LORA) {  // g and u as the unfused product stores them with its addend
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            s[j] = round_bf(round_bf(s[j]) + lt[j]);
+            u[j] = round_bf(round_bf(u[j]) + lt2[j]);
+          }
+        }
         u16x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = f2bf(round_bf(nf4_silu(round_bf(s[j]))) * round_bf(u[j]));
         *reinterpret_cast<u16x4*>(reinterpret_cast<u16*>(p.C) + r * p.ldc + n0 + 4 * g) = o;
       }
+    } else if constexpr (LORA) {
+      store4_lora(p, s, lt, r, n0 + 4 * g);
     } else {
       store4<CULLAVO_DT_BF16>(p, s, r, n0 + 4 * g);
     }
@@ -230,10 +262,17 @@ extern "C" int cullavo_nf4_dequantize(int64_t N, int64_t K, const void* codes, c
   return cullavo_check_launch("nf4_dequantize");
 }
 
-extern "C" int cullavo_nf4_decode_linear(int swiglu_out, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
-                                         const void* codes, const void* absmax, void* y, int64_t ldy,
-                                         const void* residual, int64_t ldr, const void* addend, int64_t ld_add,
-                                         void* stream) {
+
+// gemv.hip: the LoRA arguments of the decode products, checked and copied into the argument block
+int cvgemm_decode_lora_args(cvgemm::GemmArgs& p, const char* who, int64_t rows, bool swiglu_out, const void* lora_u,
+                            int64_t ld_lora_u, const void* lora_b, int64_t lora_out, int lora_r, float lora_scale);
+
+// both entry points: the epilogue's LoRA term is `addend` (materialised) or lora_u / lora_b (fused), not both
+static int nf4_decode_linear_impl(int swiglu_out, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
+                                  const void* codes, const void* absmax, void* y, int64_t ldy, const void* residual,
+                                  int64_t ldr, const void* addend, int64_t ld_add, const void* lora_u,
+                                  int64_t ld_lora_u, const void* lora_b, int64_t lora_out, int lora_r,
+                                  float lora_scale, void* stream) {
   CV_REQUIRE(swiglu_out == 0 || swiglu_out == 1, CULLAVO_EINVAL, "nf4_decode_linear: swiglu_out 0 or 1");
   CV_REQUIRE(!swiglu_out || (residual == nullptr && addend == nullptr), CULLAVO_EINVAL,
              "nf4_decode_linear: the SwiGLU output takes no residual or addend");
@@ -253,18 +292,47 @@ extern "C" int cullavo_nf4_decode_linear(int swiglu_out, int64_t M, int64_t N, i
   p.alpha = 1.f;
   p.beta = 0.f;
   p.act = CULLAVO_ACT_NONE;
+  const bool lora = lora_u != nullptr;
+  if (lora) {
+    const int rc = cvgemm_decode_lora_args(p, "nf4_decode_linear_lora", swiglu_out ? 2 * N : N, swiglu_out != 0, lora_u,
+                                           ld_lora_u, lora_b, lora_out, lora_r, lora_scale);
+    if (rc != 0) return rc;
+  }
   hipStream_t s = CV_STREAM(stream);
   const unsigned grid = (unsigned)cdiv(N, swiglu_out ? 8 : 16);
   const uint8_t* c = (const uint8_t*)codes;
   const float* a = (const float*)absmax;
   // waves per workgroup (each takes a contiguous range of K / 64 / NW blocks in batches of 8); lab
-  // switch CULLAVO_NF4_WAVES = 2 | 4 | 8 | 16, read once per process (as gemv.hip's CULLAVO_GEMV)
+  // switch CULLAVO_NF4_WAVES = 2 | 4 | 8 | 16, read once per process (as gemv.hip's CULLAVO_GEMV); the
+  // fused LoRA term runs on the shapes' own variants only
   static const int wenv = getenv("CULLAVO_NF4_WAVES") ? atoi(getenv("CULLAVO_NF4_WAVES")) : 0;
-  const int nw = (wenv == 2 || wenv == 4 || wenv == 8 || wenv == 16) ? wenv : (K > 8192 ? kNf4WavesLongK : kNf4Waves);
-#define NF4_GV(NW)                                                               \
-  if (swiglu_out) nf4_gemv_k<NW, 8, 1><<<grid, 64 * NW, 0, s>>>(p, c, a);        \
-  else nf4_gemv_k<NW, 8, 0><<<grid, 64 * NW, 0, s>>>(p, c, a);
-  if (nw == 2) { NF4_GV(2) } else if (nw == 4) { NF4_GV(4) } else if (nw == 8) { NF4_GV(8) } else { NF4_GV(16) }
+  const int nw = (!lora && (wenv == 2 || wenv == 4 || wenv == 8 || wenv == 16)) ? wenv
+                                                                                 : (K > 8192 ? kNf4WavesLongK : kNf4Waves);
+#define NF4_GVL(NW, L)                                                              \
+  if (swiglu_out) nf4_gemv_k<NW, 8, 1, L><<<grid, 64 * NW, 0, s>>>(p, c, a);        \
+  else nf4_gemv_k<NW, 8, 0, L><<<grid, 64 * NW, 0, s>>>(p, c, a);
+#define NF4_GV(NW) NF4_GVL(NW, false)
+  if (lora) {
+    if (nw == 8) { NF4_GVL(8, true) } else { NF4_GVL(16, true) }
+  } else if (nw == 2) { NF4_GV(2) } else if (nw == 4) { NF4_GV(4) } else if (nw == 8) { NF4_GV(8) } else { NF4_GV(16) }
 #undef NF4_GV
+#undef NF4_GVL
   return cullavo_check_launch("nf4_decode_linear");
+}
+
+extern "C" int cullavo_nf4_decode_linear(int swiglu_out, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
+                                         const void* codes, const void* absmax, void* y, int64_t ldy,
+                                         const void* residual, int64_t ldr, const void* addend, int64_t ld_add,
+                                         void* stream) {
+  return nf4_decode_linear_impl(swiglu_out, M, N, K, x, ldx, codes, absmax, y, ldy, residual, ldr, addend, ld_add,
+                                nullptr, 0, nullptr, 0, 0, 0.f, stream);
+}
+
+extern "C" int cullavo_nf4_decode_linear_lora(int swiglu_out, int64_t M, int64_t N, int64_t K, const void* x,
+                                              int64_t ldx, const void* codes, const void* absmax, void* y, int64_t ldy,
+                                              const void* residual, int64_t ldr, const void* lora_u, int64_t ld_lora_u,
+                                              const void* lora_b, int64_t lora_out, int lora_r, float lora_scale,
+                                              void* stream) {
+  return nf4_decode_linear_impl(swiglu_out, M, N, K, x, ldx, codes, absmax, y, ldy, residual, ldr, nullptr, 0, lora_u,
+                                ld_lora_u, lora_b, lora_out, lora_r, lora_scale, stream);
 }

@@ -56,7 +56,7 @@ import torch
 
 from . import ops
 from .functions import StepContext
-from .lora import NO_LORA
+from .lora import NO_LORA, LoraTerm
 
 import os
 
@@ -71,11 +71,16 @@ import os
 #           norm launch: off by default). A norm in the TAIL of o_proj / down_proj instead (the last
 #           workgroup by an agent-scope counter normalises the rows) measured 3.78 vs 3.53 ms
 #           (profiles/r05/decode/pnorm_ab_*): not kept
-_FUSE = {f.strip() for f in os.environ.get("CULLAVO_DECODE_FUSE", "gu,rope").split(",") if f.strip()}
+#   "lora"  (default on) the adapters' up-projection t = scaling * u_m B_m^T in the epilogue of the
+#           group's weight-streaming product (cullavo_decode_linear_lora / cullavo_nf4_decode_linear_lora)
+#           instead of one K = 64 product per module into an [M, N] addend; with it the fusions above
+#           hold for a model with adapters too. Off: the materialised addend (LoraTerm.materialize).
+_FUSE = {f.strip() for f in os.environ.get("CULLAVO_DECODE_FUSE", "gu,rope,lora").split(",") if f.strip()}
 FUSE_DECODE_NORMS = "norm" in _FUSE
 FUSE_DECODE_SWIGLU = "swiglu" in _FUSE
 FUSE_DECODE_GU = "gu" in _FUSE
 FUSE_DECODE_ROPE = "rope" in _FUSE
+FUSE_DECODE_LORA = "lora" in _FUSE
 # CULLAVO_NF4_DECODE=0: a model quantised by quant.quantize_lm_nf4_ decodes through the bf16 GEMV on
 # its (dequantised) arena weights instead of the 4-bit product on the NF4 copies (A/B switch)
 NF4_DECODE = os.environ.get("CULLAVO_NF4_DECODE", "1") != "0"
@@ -249,14 +254,43 @@ def new_chunk_padding(attention_mask, Lnew: int):
     return lead.to(torch.int32)
 
 
-def _nf4_linear(q, x, w, group, residual=None):
+def _decode_lora(t, M: int, rows: int):
+    """The lora= arguments that put a group's LoRA term t into the epilogue of its decode product
+    (ops.decode_linear, M rows on a weight of `rows` rows), or None: no adapters, FUSE_DECODE_LORA
+    off (read per call: tests patch it), or a group the kernels do not take (LoraTerm.decode_args:
+    r != 64, uneven modules), whose term is then materialised as before."""
+    if t is None or not FUSE_DECODE_LORA:
+        return None
+    return t.decode_args(M, rows)
+
+
+def _nf4_linear(q, x, w, group, residual=None, gemv: bool = False):
     """One Linear of the decode step: on the NF4 copy q = (codes, absmax) when the layer has one
-    (the LoRA term materialised and passed as the epilogue addend; w goes along, so a shape on which
-    the bf16 GEMV measured faster stays there, ops.NF4_BF16_FASTER), else ops.linear on w."""
+    (w goes along, so a shape on which the bf16 GEMV measured faster stays there,
+    ops.NF4_BF16_FASTER), else on w. gemv: these are decode rows. The group's LoRA term rides in the
+    product's epilogue (_decode_lora; ops.nf4_decode_linear takes the LoraTerm itself and decides the
+    same way) or, where it cannot, is materialised and passed as the epilogue addend."""
     t, _ = group.forward(x, False, 0)
     if q is None:
+        la = _decode_lora(t, x.shape[0], w.shape[0]) if gemv else None
+        if la is not None:
+            return ops.decode_linear(x, w, residual=residual, lora=la)
         return ops.linear(x, w, residual=residual, addend=t)
-    return ops.nf4_decode_linear(x, q[0], q[1], residual=residual, addend=None if t is None else t.materialize(), w=w)
+    if t is not None and not FUSE_DECODE_LORA:
+        t = t.materialize()
+    return ops.nf4_decode_linear(x, q[0], q[1], residual=residual, addend=t, w=w)
+
+
+def _norm_lora(group, h, norm_w, eps: float, rows: int):
+    """FUSE_DECODE_NORMS with adapters: u = RMSNorm(h) A^T by the norm-fused product on the group's
+    lora_A stack (one launch, no normalised rows in HBM) and the lora= arguments it gives."""
+    if group is NO_LORA:
+        return None
+    u = ops.decode_linear(h, group.a_stack(), transform=1, norm_w=norm_w, eps=eps)
+    la = LoraTerm(group, u).decode_args(h.shape[0], rows)
+    if la is None:
+        raise RuntimeError("layer_infer: a group that passed decode_fusable() gave no decode arguments")
+    return la
 
 
 # The attention routes of a chunk of new rows: decided once per chunk (by lm_infer's callees and the
@@ -298,14 +332,18 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, route: str
     # round-4 per-fragment form was ~2x slower, profiles/r04/decode/decode_fusions_ab.txt) for the
     # rows that fit LDS (M (d + 8) * 2 <= 64 KiB); FUSE_DECODE_SWIGLU: the SwiGLU in down_proj's
     # X loads (transform 2), only without FUSE_DECODE_GU. All bitwise the unfused values.
+    # Adapters (FUSE_DECODE_LORA): every product takes its group's term in its epilogue, so these
+    # fusions hold with them; u = T(x) A^T comes from the same transform on the lora_A stack.
     fused = (FUSE_DECODE_NORMS and gemv and h.shape[0] * (d + 8) * 2 <= 65536 and not nf4
-             and all(g is NO_LORA for g in lg.values()))
+             and all(g is NO_LORA or (FUSE_DECODE_LORA and g.decode_fusable()) for g in lg.values()))
+    M = h.shape[0]
     if fused:
-        qkv = ops.decode_linear(h, layer.w_qkv(), transform=1, norm_w=layer.input_layernorm.weight,
-                                eps=cfg.rms_norm_eps)
+        norm1 = dict(transform=1, norm_w=layer.input_layernorm.weight, eps=cfg.rms_norm_eps)
+        qkv = ops.decode_linear(h, layer.w_qkv(), **norm1,
+                                lora=_norm_lora(lg["qkv"], h, norm1["norm_w"], norm1["eps"], 3 * d))
     else:
         x1, _ = ops.rmsnorm_fwd(h, layer.input_layernorm.weight, cfg.rms_norm_eps)
-        qkv = _nf4_linear(nf4.get("qkv"), x1, layer.w_qkv(), lg["qkv"])
+        qkv = _nf4_linear(nf4.get("qkv"), x1, layer.w_qkv(), lg["qkv"], gemv=gemv)
     q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
     kc, vc, pos = cache.k[li], cache.v[li], sctx.position_ids
     rope = dict(head_dim=D, theta=cfg.rope_theta)
@@ -334,30 +372,45 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, route: str
         o = ops.attn_decode(q, kc, vc, kv_len, max_len=attn_len, **attn)
     else:
         raise ValueError(f"layer_infer: unknown attention route {route!r}")
-    h2 = _nf4_linear(nf4.get("o"), o, layer.self_attn.o_proj.weight, lg["o"], residual=h)
+    h2 = _nf4_linear(nf4.get("o"), o, layer.self_attn.o_proj.weight, lg["o"], residual=h, gemv=gemv)
+    w_gu, w_down = layer.w_gu(), layer.mlp.down_proj.weight
+    F2 = w_gu.shape[0]
     if fused:
+        norm2 = dict(norm_w=layer.post_attention_layernorm.weight, eps=cfg.rms_norm_eps)
+        la = _norm_lora(lg["gu"], h2, norm2["norm_w"], norm2["eps"], F2)
         if FUSE_DECODE_GU:  # RMSNorm, gate|up product and SwiGLU in one launch (transform 4)
-            a = ops.decode_linear(h2, layer.w_gu(), transform=4, norm_w=layer.post_attention_layernorm.weight,
-                                  eps=cfg.rms_norm_eps)
-            return ops.linear(a, layer.mlp.down_proj.weight, residual=h2)
-        gu = ops.decode_linear(h2, layer.w_gu(), transform=1, norm_w=layer.post_attention_layernorm.weight,
-                               eps=cfg.rms_norm_eps)
+            a = ops.decode_linear(h2, w_gu, transform=4, **norm2, lora=la)
+            return _nf4_linear(None, a, w_down, lg["down"], residual=h2, gemv=True)
+        gu = ops.decode_linear(h2, w_gu, transform=1, **norm2, lora=la)
         if FUSE_DECODE_SWIGLU:
-            return ops.decode_linear(gu, layer.mlp.down_proj.weight, transform=2, residual=h2)
-        return ops.linear(ops.swiglu_fwd(gu), layer.mlp.down_proj.weight, residual=h2)
+            ld = None
+            if lg["down"] is not NO_LORA:  # u = SwiGLU(gu) A^T by the same fused X loads
+                ld = LoraTerm(lg["down"], ops.decode_linear(gu, lg["down"].a_stack(), transform=2)).decode_args(M, d)
+            return ops.decode_linear(gu, w_down, transform=2, residual=h2, lora=ld)
+        return _nf4_linear(None, ops.swiglu_fwd(gu), w_down, lg["down"], residual=h2, gemv=True)
     x2, _ = ops.rmsnorm_fwd(h2, layer.post_attention_layernorm.weight, cfg.rms_norm_eps)
     t, _ = lg["gu"].forward(x2, False, 0)
+    la = _decode_lora(t, M, F2) if gemv else None
+    # gate|up product (+ the adapters' term) + SwiGLU in one launch of the bf16 GEMV: a layer without an
+    # NF4 copy, or adapters on a shape where that GEMV measured faster than the NF4 product
+    one_launch = gemv and FUSE_DECODE_GU and (t is None or la is not None)
     if "gu" in nf4:
+        one_launch = one_launch and t is not None and ops.nf4_prefers_bf16(F2, d, M)
+    if one_launch:
+        a = ops.decode_linear(x2, w_gu, transform=3, lora=la)
+    elif "gu" in nf4:
         if t is None:  # gate|up product + SwiGLU in one launch
-            a = ops.nf4_decode_linear(x2, *nf4["gu"], swiglu_out=True, w=layer.w_gu())
+            a = ops.nf4_decode_linear(x2, *nf4["gu"], swiglu_out=True, w=w_gu)
         else:
-            a = ops.swiglu_fwd(ops.nf4_decode_linear(x2, *nf4["gu"], addend=t.materialize(), w=layer.w_gu()))
-    elif FUSE_DECODE_GU and t is None and gemv:
-        a = ops.decode_linear(x2, layer.w_gu(), transform=3)  # gate|up product + SwiGLU, one launch
+            # adapters on the NF4 product: the term in its epilogue, the SwiGLU its own launch (an adapter
+            # model's NF4 calls carry an addend and no SwiGLU output: tests/test_nf4.py pins that)
+            a = ops.swiglu_fwd(ops.nf4_decode_linear(x2, *nf4["gu"], w=w_gu,
+                                                     addend=t if FUSE_DECODE_LORA else t.materialize()))
+    elif la is not None:
+        a = ops.swiglu_fwd(ops.decode_linear(x2, w_gu, lora=la))
     else:
-        gu = ops.linear(x2, layer.w_gu(), addend=t)
-        a = ops.swiglu_fwd(gu)
-    return _nf4_linear(nf4.get("down"), a, layer.mlp.down_proj.weight, lg["down"], residual=h2)
+        a = ops.swiglu_fwd(ops.linear(x2, w_gu, addend=t))
+    return _nf4_linear(nf4.get("down"), a, w_down, lg["down"], residual=h2, gemv=gemv)
 
 
 SAMPLE_TOP_K_MAX = 1024  # cullavo_sample_token: 1 <= top_k <= 1024
@@ -490,6 +543,10 @@ class DecodeGraph:
         # for the graph's lifetime even if quant.nf4_weights() drops them from the layers meanwhile
         from .quant import nf4_weights
         self.nf4_refs = [nf4_weights(layer) for layer in lm.model.layers] if NF4_DECODE else []
+        # adapters: the captured products read lora_A / lora_B (FUSE_DECODE_LORA: in their epilogues, the
+        # same route as the eager step, decided by layer_infer at capture) straight from the LoRA arena,
+        # whose storage the model owns and never reallocates: it outlives the graph, and a replay after a
+        # training step computes with the adapters as that step left them
         self.graph = torch.cuda.CUDAGraph()
         self.steps_left = cache.max_len - cache.length
         stream = torch.cuda.Stream(device=dev)

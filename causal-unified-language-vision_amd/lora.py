@@ -146,6 +146,18 @@ class LoraTerm:
             return None
         return self.u, g.b_stack(), w, g.scaling
 
+    def decode_args(self, M: int, N: int):
+        """fused_args' counterpart for the decode rows (1 <= M <= 16): the lora= tuple of
+        ops.decode_linear / ops.nf4_decode_linear, whose kernels add the term in the weight-streaming
+        product's epilogue, or None where they do not take it (r != 64, modules of unequal width or
+        not a multiple of 16 wide, N not the group's rows, u not bf16 or its row stride off 8).
+        N: the weight's rows (the gate|up product with a SwiGLU output included: 2F)."""
+        g = self.group
+        if (not g.decode_fusable() or not 1 <= M <= 16 or N != g.out_total
+                or self.u.dtype != torch.bfloat16 or ops._ld(self.u) % 8):
+            return None
+        return self.u, g.b_stack(), g.outs[0], g.scaling
+
     def materialize(self):
         return self.group.up_project(self.u)
 
@@ -210,6 +222,12 @@ class LoraGroup:
 
     def b_stack(self):
         return self.arena.view(self.b_keys[0], (self.out_total, self.r))
+
+    def decode_fusable(self) -> bool:
+        """the group's part of LoraTerm.decode_args: r = 64 and modules of one width, a multiple of 16
+        (a decode workgroup's 16 weight rows then lie in one module)"""
+        w = self.outs[0]
+        return self.r == 64 and all(o == w for o in self.outs) and w % 16 == 0
 
     def backward(self, dy, x, u, dx, train: bool, step_seed: int):
         """Writes dA / dB into the arena's gradient slots and accumulates the adapters' share of

@@ -425,18 +425,55 @@ def lora_dx(du, a_stack, dx, *, n_mod: int, drop_p: float, seeds):
     return dx
 
 
-def decode_linear(x, w, *, transform: int = 0, norm_w=None, eps: float = 0.0, residual=None):
+def _decode_lora_args(name: str, lora, x):
+    """the C arguments of lora = (u, b_stack, module_width, scale), the tuple LoraTerm.fused_args /
+    decode_args build: (u, ld_u, b_stack, module width, r, scale). The shape rules are the library's
+    (CULLAVO_EUNSUPPORTED before any launch); what it cannot see -- dtypes, a lora_B stack that is not
+    the contiguous [rows, r] array it indexes -- is refused here."""
+    u, bst, width, scale = lora
+    _dev(u, bst)
+    if u.dtype != torch.bfloat16 or bst.dtype != torch.bfloat16 or x.dtype != torch.bfloat16:
+        raise TypeError(f"{name}: the fused LoRA term takes bf16 rows, u and lora_B (got {x.dtype}, {u.dtype}, "
+                        f"{bst.dtype})")
+    if u.dim() != 2 or u.shape[0] != x.shape[0]:
+        raise ValueError(f"{name}: u {tuple(u.shape)} against {x.shape[0]} rows")
+    if bst.dim() != 2 or not bst.is_contiguous():
+        raise ValueError(f"{name}: lora_B must be the contiguous [rows, r] stack")
+    return _ptr(u), _ld(u), _ptr(bst), int(width), int(bst.shape[1]), float(scale)
+
+
+def _decode_out(name: str, out, M: int, N: int, like):
+    """the decode products' output: a fresh [M, N], or the caller's 2-D view of that shape and dtype"""
+    if out is None:
+        return torch.empty((M, N), dtype=like.dtype, device=like.device)
+    _dev(out)
+    if out.dtype != like.dtype or tuple(out.shape) != (M, N):
+        raise ValueError(f"{name}: out must be {like.dtype} [{M}, {N}], got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def decode_linear(x, w, *, transform: int = 0, norm_w=None, eps: float = 0.0, residual=None, lora=None, out=None):
     """Decode rows (M <= 16) through cullavo_decode_linear: y = T(x) @ w.T (+ residual) with T the
     fused input transform (0 none, 1 RMSNorm with norm_w / eps, 2 SwiGLU of x = gate|up [M, 2K]);
-    transform 3: y = SwiGLU(x @ w.T) for the fused gate|up weight w [2N, K] (y [M, N]); 4: 1 and 3."""
+    transform 3: y = SwiGLU(x @ w.T) for the fused gate|up weight w [2N, K] (y [M, N]); 4: 1 and 3.
+    lora = (u, b_stack, module_width, scale) (LoraTerm.decode_args): the adapters' term
+    scale * u_m @ B_m.T in the product's epilogue (cullavo_decode_linear_lora), bitwise
+    linear(T(x), w, addend=up_project(u), residual=...) -- with transform 3 / 4 followed by swiglu_fwd.
+    out: a [M, N] view to write instead of a fresh tensor."""
     _dev(x, w, norm_w, residual)
     M = x.shape[0]
     N, K = w.shape
     if transform in (3, 4):
         N //= 2
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    call("decode_linear", int(transform), M, N, K, _ptr(x), _ld(x), _ptr(norm_w), float(eps), _ptr(w), _ld(w),
-         _ptr(y), _ld(y), _ptr(residual), _ld(residual) if residual is not None else 0, _stream())
+    y = _decode_out("decode_linear", out, M, N, x)
+    args = (int(transform), M, N, K, _ptr(x), _ld(x), _ptr(norm_w), float(eps), _ptr(w), _ld(w),
+            _ptr(y), _ld(y), _ptr(residual), _ld(residual) if residual is not None else 0)
+    if lora is not None:
+        if lora[1].shape[0] != w.shape[0]:
+            raise ValueError(f"decode_linear: lora_B stack {tuple(lora[1].shape)} against {w.shape[0]} weight rows")
+        call("decode_linear_lora", *args, *_decode_lora_args("decode_linear", lora, x), _stream())
+    else:
+        call("decode_linear", *args, _stream())
     return y
 
 
@@ -494,13 +531,26 @@ def nf4_prefers_bf16(rows: int, K: int, M: int) -> bool:
     return M <= NF4_BF16_FASTER.get((rows, K), 0)
 
 
-def nf4_decode_linear(x, codes, absmax, *, residual=None, addend=None, swiglu_out: bool = False, w=None):
+def nf4_decode_linear(x, codes, absmax, *, residual=None, addend=None, swiglu_out: bool = False, w=None, lora=None,
+                      out=None):
     """Decode rows (M <= 16, bf16) on an NF4 weight through cullavo_nf4_decode_linear:
     y = x @ dq(W).T with the LoRA term `addend` and `residual` added as ops.linear adds them;
     swiglu_out: the weight is the fused gate|up [2N, K] and y [M, N] = SwiGLU(x @ dq(W).T).
     w: the dequantised bf16 weight [rows, K] (the arena's), when the caller has it: a shape on
     which the bf16 GEMV measured faster (NF4_BF16_FASTER) then runs there instead, on the
-    same values rounded to bf16."""
+    same values rounded to bf16.
+    lora = (u, b_stack, module_width, scale) (LoraTerm.decode_args): the term in the product's epilogue
+    (cullavo_nf4_decode_linear_lora) instead of a materialised addend, bitwise the same; with
+    swiglu_out the term joins g and u before the SwiGLU. As with ops.linear, `addend` may be a
+    lora.LoraTerm: it is fused when its decode_args() allow and materialised otherwise.
+    out: a [M, N] view to write instead of a fresh tensor."""
+    if addend is not None and hasattr(addend, "decode_args"):
+        if lora is not None:
+            raise ValueError("nf4_decode_linear: a LoraTerm addend and lora= exclude each other")
+        lora = addend.decode_args(x.shape[0], codes.shape[0])
+        addend = None if lora is not None else addend.materialize()
+    if lora is not None and addend is not None:
+        raise ValueError("nf4_decode_linear: lora= replaces the materialised addend")
     _dev(x, codes, absmax, residual, addend, w)
     if x.dtype != torch.bfloat16:
         raise TypeError(f"nf4_decode_linear: bf16 rows only, got {x.dtype}")
@@ -528,13 +578,18 @@ def nf4_decode_linear(x, codes, absmax, *, residual=None, addend=None, swiglu_ou
         if w.dtype != torch.bfloat16 or tuple(w.shape) != (rows, K):
             raise ValueError(f"nf4_decode_linear: w must be the bf16 [{rows}, {K}] weight")
         if nf4_prefers_bf16(rows, K, M):
-            if swiglu_out:
-                return decode_linear(x, w, transform=3)
-            return linear(x, w, residual=residual, addend=addend)
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    call("nf4_decode_linear", int(bool(swiglu_out)), M, N, K, _ptr(x), _ld(x), _ptr(codes), _ptr(absmax), _ptr(y),
-         _ld(y), _ptr(residual), _ld(residual) if residual is not None else 0, _ptr(addend),
-         _ld(addend) if addend is not None else 0, _stream())
+            if swiglu_out or lora is not None:
+                return decode_linear(x, w, transform=3 if swiglu_out else 0, residual=residual, lora=lora, out=out)
+            return linear(x, w, residual=residual, addend=addend, out=out)
+    y = _decode_out("nf4_decode_linear", out, M, N, x)
+    args = (int(bool(swiglu_out)), M, N, K, _ptr(x), _ld(x), _ptr(codes), _ptr(absmax), _ptr(y), _ld(y),
+            _ptr(residual), _ld(residual) if residual is not None else 0)
+    if lora is not None:
+        if lora[1].shape[0] != rows:
+            raise ValueError(f"nf4_decode_linear: lora_B stack {tuple(lora[1].shape)} against {rows} weight rows")
+        call("nf4_decode_linear_lora", *args, *_decode_lora_args("nf4_decode_linear", lora, x), _stream())
+    else:
+        call("nf4_decode_linear", *args, _ptr(addend), _ld(addend) if addend is not None else 0, _stream())
     return y
 
 

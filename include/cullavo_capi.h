@@ -63,7 +63,9 @@ extern "C" {
    was added under 8 without a bump, as cullavo_lora_dx was under its version: a pure addition that
    changes no existing signature; so were cullavo_attn_fwd_ragged and cullavo_kv_append_ragged under 9
    (the ragged KV cache: two new entry points, nothing existing touched), and cullavo_attn_fwd_varlen,
-   cullavo_attn_bwd_varlen and cullavo_attn_varlen_set_check (packed training sequences). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
+   cullavo_attn_bwd_varlen and cullavo_attn_varlen_set_check (packed training sequences), and
+   cullavo_decode_linear_lora and cullavo_nf4_decode_linear_lora (the decode products with the LoRA
+   up-projection in their epilogue). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
 #define CULLAVO_ABI_VERSION 9
 
 int cullavo_abi_version(void);
@@ -471,6 +473,25 @@ int cullavo_attn_varlen_set_check(int on);
 int cullavo_decode_linear(int x_transform, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
                           const void* norm_w, float eps, const void* W, int64_t ldw, void* y, int64_t ldy,
                           const void* residual, int64_t ldr, void* stream);
+/* cullavo_decode_linear with the LoRA up-projection in its epilogue (added under ABI 9, additive: the
+ * decode step of the model the reference generates with -- peft LoRA, r = 64, lora_alpha = 16, on all
+ * seven Linears of every decoder layer, cullavo/load_cullavo.py:103-112, whose generate() the
+ * step-2 pre-labelling calls, cullavo/arch_cullavo.py:362-365, through the cached forward :605-636).
+ * lora_u [M, n_modules * 64] bf16 (row stride ld_lora_u) holds the lora_A outputs of the Linears that
+ * share x, lora_b [N_total, 64] bf16 contiguous their lora_B weights stacked in output order; output
+ * column n belongs to module n / lora_out and
+ *   y = bf16(bf16(bf16(acc) + t) + residual),  t = bf16(lora_scale * sum_j u[b][64 m + j] lora_b[n][j]),
+ * bit for bit cullavo_gemm_ex with `addend` = the K = 64 product cullavo_gemm_ex(alpha = lora_scale)
+ * of u and lora_b (the sum in that product's order), without its launches or the [M, N] round trip.
+ * x_transform 0 / 1 / 2 act on x only; 3 / 4: the group is gate | up (two modules of N rows) and the
+ * term is added to g and u before the SwiGLU, each rounded as that addend path rounds it.
+ * lora_u NULL: cullavo_decode_linear. Otherwise lora_r == 64, lora_out % 16 == 0,
+ * N == n_modules * lora_out (3 / 4: lora_out == N) and ld_lora_u % 8 == 0, else CULLAVO_EUNSUPPORTED;
+ * lora_b NULL, ld_lora_u < n_modules * 64 or a pointer off 16 bytes: CULLAVO_EINVAL. Before any launch. */
+int cullavo_decode_linear_lora(int x_transform, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
+                               const void* norm_w, float eps, const void* W, int64_t ldw, void* y, int64_t ldy,
+                               const void* residual, int64_t ldr, const void* lora_u, int64_t ld_lora_u,
+                               const void* lora_b, int64_t lora_out, int lora_r, float lora_scale, void* stream);
 /* ---- NF4 base weights (ABI 5) ----------------------------------------------------------------
  * The reference's LM never runs on bf16 base weights: every decoder-layer Linear is bitsandbytes
  * NF4 with bf16 compute, lm_head and the projector skipped (cullavo/load_cullavo.py:66-83). The
@@ -497,6 +518,18 @@ int cullavo_nf4_decode_linear(int swiglu_out, int64_t M, int64_t N, int64_t K, c
                               const void* codes, const void* absmax, void* y, int64_t ldy,
                               const void* residual, int64_t ldr, const void* addend, int64_t ld_addend,
                               void* stream);
+/* cullavo_nf4_decode_linear with the LoRA up-projection in its epilogue instead of a materialised
+ * addend (added under ABI 9, additive): the decode step of the reference's own model, NF4 base
+ * weights plus peft LoRA r = 64 (prepare_cullavo(bits=4, lora=True), cullavo/load_cullavo.py:63-112;
+ * generate() at cullavo/arch_cullavo.py:362-365). lora_* and the error codes as
+ * cullavo_decode_linear_lora; swiglu_out 1: the gate | up pair, the term added before the SwiGLU.
+ * Bit for bit cullavo_nf4_decode_linear with the term as `addend` (swiglu_out 1: followed by
+ * cullavo_swiglu_fwd). lora_u NULL: cullavo_nf4_decode_linear without an addend. */
+int cullavo_nf4_decode_linear_lora(int swiglu_out, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
+                                   const void* codes, const void* absmax, void* y, int64_t ldy,
+                                   const void* residual, int64_t ldr, const void* lora_u, int64_t ld_lora_u,
+                                   const void* lora_b, int64_t lora_out, int lora_r, float lora_scale,
+                                   void* stream);
 size_t cullavo_attn_decode_workspace(int B, int H, int max_len, int D);
 int cullavo_attn_decode(const void* q, int64_t ldq, const void* k_cache, const void* v_cache, int64_t ld_tok,
                         int64_t ld_batch, const int32_t* kv_len, const int32_t* kv_start, void* o, int64_t ldo,
