@@ -84,6 +84,10 @@ class CuLLaVOModel(nn.Module):
         self.packed_rows = False
         # rows per piece of a cached forward's prefill (None: one pass; generate(prefill_chunk=N))
         self.prefill_chunk = None
+        # the KV cache a cached forward / generate() creates when the call does not say (kv_cache_dtype=):
+        # "bf16", "fp8" (e4m3 codes with a power-of-two scale per token and head, half the bytes) or
+        # "fp8_sim" (fp8's numerics on a bf16 cache); generation.KVCache
+        self.kv_cache_dtype = "bf16"
 
     @classmethod
     def from_pretrained(cls, path: str, *, device="cuda", trainable: str = "full", lora: LoraSettings | None = None,
@@ -176,8 +180,11 @@ class CuLLaVOModel(nn.Module):
     def forward(self, input_ids=None, pixel_values=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, vision_feature_layer=None, vision_feature_select_strategy=None, labels=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None,
-                num_supervised: int | None = None, attended_lens=None):
-        """num_supervised: host-side upper bound of the number of label positions of this batch (counted
+                num_supervised: int | None = None, attended_lens=None, kv_cache_dtype: str | None = None):
+        """kv_cache_dtype (with use_cache / past_key_values only): the format of the KV cache this call
+        creates -- None: self.kv_cache_dtype; a KVCache passed as past_key_values keeps its own format and
+        a conflicting value raises ValueError.
+        num_supervised: host-side upper bound of the number of label positions of this batch (counted
         where the batch is built). With self.supervised_rows set (the trainer's opt-in) the loss then
         comes from those rows only and the output carries no logits.
         With self.packed_rows set, a batch with padding is packed: embeddings, the image merge, position
@@ -199,7 +206,10 @@ class CuLLaVOModel(nn.Module):
                     else cfg.vision_feature_select_strategy)
         if past_key_values is not None or use_cache:
             return self._forward_cached(input_ids, pixel_values, attention_mask, position_ids, past_key_values,
-                                        inputs_embeds, vision_feature_layer, strategy, labels, return_dict)
+                                        inputs_embeds, vision_feature_layer, strategy, labels, return_dict,
+                                        kv_cache_dtype=kv_cache_dtype)
+        if kv_cache_dtype is not None:
+            raise ValueError("kv_cache_dtype goes with use_cache=True or past_key_values (this forward keeps no cache)")
         if output_attentions:
             raise NotImplementedError("flash attention never materialises attention probabilities")
 
@@ -356,19 +366,20 @@ class CuLLaVOModel(nn.Module):
     # -- KV-cache inference (reference :605-636 and HF generate; generation.py) ------------------
     def _forward_cached(self, input_ids, pixel_values, attention_mask, position_ids, cache, inputs_embeds,
                         vision_feature_layer, strategy, labels, return_dict, max_len: int | None = None,
-                        prefill_chunk: int | None = None):
+                        prefill_chunk: int | None = None, kv_cache_dtype: str | None = None):
         from .generation import KVCache, lm_infer
+        kv_dtype = self._kv_dtype(cache, kv_cache_dtype)
         if cache is not None and not isinstance(cache, KVCache):
             # transformers-layout cache (legacy tuple / DynamicCache, as the reference's decode branch
             # receives it, arch_cullavo.py:605-636): copied once; the KVCache returned in
             # past_key_values indexes like the legacy tuple (cache[layer] -> (key, value) [B,H,L,D])
-            cache = KVCache.from_legacy(cache, attention_mask)
+            cache = KVCache.from_legacy(cache, attention_mask, kv_dtype=kv_dtype)
         if torch.is_grad_enabled() and any(p.requires_grad for ar in self.arenas.values() for p in ar.params.values()):
             torch.set_grad_enabled(False)  # inference only, as under the reference's torch.inference_mode()
             try:
                 return self._forward_cached(input_ids, pixel_values, attention_mask, position_ids, cache,
                                             inputs_embeds, vision_feature_layer, strategy, labels, return_dict,
-                                            max_len, prefill_chunk)
+                                            max_len, prefill_chunk, kv_dtype)
             finally:
                 torch.set_grad_enabled(True)
         self.vision_tower.eval()
@@ -383,10 +394,26 @@ class CuLLaVOModel(nn.Module):
         if max_len is None:
             max_len = L + 256
         logits, cache = lm_infer(self.language_model, inputs_embeds, attention_mask, position_ids, cache, max_len,
-                                 prefill_chunk if prefill_chunk is not None else self.prefill_chunk)
+                                 prefill_chunk if prefill_chunk is not None else self.prefill_chunk, kv_dtype=kv_dtype)
         out = CullavoCausalLMOutputWithPast(loss=None, logits=logits, past_key_values=cache, hidden_states=None,
                                             attentions=None)
         return out if return_dict else out.to_tuple()
+
+    def _kv_dtype(self, cache, kv_cache_dtype: str | None) -> str:
+        """the KV-cache format of a cached call: the caller's, else a KVCache's own, else the model's
+        default; a KVCache of another format than the caller names is a ValueError"""
+        from .generation import KV_DTYPES, KVCache
+        if kv_cache_dtype is not None and kv_cache_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}: one of {KV_DTYPES}")
+        if isinstance(cache, KVCache):
+            if kv_cache_dtype is not None and kv_cache_dtype != cache.kv_dtype:
+                raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r} conflicts with the {cache.kv_dtype!r} cache passed "
+                                 f"as past_key_values (a cache keeps its format)")
+            return cache.kv_dtype
+        kv_dtype = kv_cache_dtype if kv_cache_dtype is not None else self.kv_cache_dtype
+        if kv_dtype != "bf16" and self.dtype != torch.bfloat16:
+            raise NotImplementedError("KV-cache decode runs on the bf16 model (the f32 mode is a parity mode)")
+        return kv_dtype
 
     @torch.no_grad()
     def generate(self, input_ids=None, pixel_values=None, attention_mask=None, max_new_tokens: int = 20,
@@ -394,7 +421,7 @@ class CuLLaVOModel(nn.Module):
                  eos_token_id: int | None = None, pad_token_id: int | None = None, use_cache: bool = True,
                  generator=None, past_key_values=None, return_dict_in_generate: bool = False,
                  prefill_chunk: int | None = None, seed: int | None = None, device_loop: bool | None = None,
-                 compact_cache: bool = False, **kw):
+                 compact_cache: bool = False, kv_cache_dtype: str | None = None, **kw):
         """Decoder-only generate: returns [B, S + new] (prompt ids then sampled ids), stopping when
         every sequence has produced eos_token_id (finished rows are padded with pad_token_id).
         past_key_values: the cache of an earlier call continues a conversation -- input_ids then holds
@@ -417,7 +444,9 @@ class CuLLaVOModel(nn.Module):
         sequences are those of compact_cache=False. generate(past_key_values=<that cache>,
         input_ids=<the left-padded new turns>, attention_mask=<[B, S] or [B, past + S]>) then
         continues every conversation; a ragged input cache or a left-padded new turn takes the
-        ragged path without the flag."""
+        ragged path without the flag.
+        kv_cache_dtype: the KV cache's format, "bf16", "fp8" or "fp8_sim" (None: self.kv_cache_dtype, or
+        the format of the KVCache passed as past_key_values; a conflicting value raises ValueError)."""
         from .generation import DecodeStepper, HostSampler, KVCache, SamplerState, device_sampling
         if not use_cache:
             raise NotImplementedError("generate() runs on the KV cache (use_cache=True)")
@@ -438,14 +467,16 @@ class CuLLaVOModel(nn.Module):
         if past_key_values is None:
             out = self._forward_cached(input_ids, pixel_values, attention_mask, None, None, None,
                                        cfg.vision_feature_layer, strategy, None, True,
-                                       max_len=L0 + max_new_tokens, prefill_chunk=prefill_chunk)
+                                       max_len=L0 + max_new_tokens, prefill_chunk=prefill_chunk,
+                                       kv_cache_dtype=kv_cache_dtype)
         else:
             if pixel_values is not None:
                 raise NotImplementedError("generate(past_key_values=...) continues with text only: the images "
                                           "are in the cache")
             cache = past_key_values
+            kv_dtype = self._kv_dtype(cache, kv_cache_dtype)
             if not isinstance(cache, KVCache):
-                cache = KVCache.from_legacy(cache, attention_mask)
+                cache = KVCache.from_legacy(cache, attention_mask, kv_dtype=kv_dtype)
             # room for the new turn and every new token before the decode graph captures the cache
             cache.grow(cache.length + S + max_new_tokens)
             out = self._forward_cached(input_ids, None, attention_mask, None, cache, None, cfg.vision_feature_layer,

@@ -97,14 +97,35 @@ def left_pad_span(mask, message: str):
     return first, count
 
 
+KV_DTYPES = ("bf16", "fp8", "fp8_sim")
+
+
 class KVCache:
     """Per-layer K, V [B, Lmax, H*D] in HBM plus the per-row state the decode kernels read. The state
     moves through methods only: begin (prefill), advance / advance_ragged (rows appended), reserve /
-    grow (capacity), adopt / mark / release (the hand-over to a decode graph and back)."""
+    grow (capacity), adopt / mark / release (the hand-over to a decode graph and back).
+    kv_dtype (INTEGRATION.md "FP8 KV cache"): "bf16" -- k, v hold the rows as they are; "fp8" -- k, v
+    hold e4m3 codes (uint8) and k_exp, v_exp [layers, B, Lmax, H] one power-of-two exponent per token
+    and head (uint8, e + 127), half the bytes; "fp8_sim" -- a bf16 cache whose appends quantise and
+    dequantise, the numerics-identical twin of "fp8" on the bf16 kernels. The bookkeeping is the same
+    for all three."""
 
-    def __init__(self, n_layers: int, B: int, max_len: int, H: int, D: int, device, dtype=torch.bfloat16):
-        self.k = torch.empty((n_layers, B, max_len, H * D), dtype=dtype, device=device)
+    def __init__(self, n_layers: int, B: int, max_len: int, H: int, D: int, device, dtype=torch.bfloat16,
+                 kv_dtype: str = "bf16"):
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype {kv_dtype!r}: one of {KV_DTYPES}")
+        if kv_dtype != "bf16" and (dtype != torch.bfloat16 or D != 128):
+            raise NotImplementedError(f"kv_dtype {kv_dtype!r} quantises bf16 rows of head_dim 128 (got {dtype}, "
+                                      f"head_dim {D})")
+        self.kv_dtype = kv_dtype
+        self.k = torch.empty((n_layers, B, max_len, H * D), dtype=torch.uint8 if kv_dtype == "fp8" else dtype,
+                             device=device)
         self.v = torch.empty_like(self.k)
+        self.k_exp = self.v_exp = None
+        if kv_dtype == "fp8":
+            self.k_exp = torch.empty((n_layers, B, max_len, H), dtype=torch.uint8, device=device)
+            self.v_exp = torch.empty_like(self.k_exp)
+        self._slab = None                    # fp8: the bf16 scratch the multi-token routes attend (dequant)
         self.B, self.max_len, self.H, self.D = B, max_len, H, D
         self.length = 0                      # rows written: every sequence's, or max(lengths) when ragged
         self.lengths = None                  # int32 [B]: rows written per sequence (None: `length` for all)
@@ -115,16 +136,52 @@ class KVCache:
         return self.k.shape[0]
 
     def __getitem__(self, layer: int):
-        """HF legacy view: (key, value) as [B, H, L, D] over the filled rows."""
+        """HF legacy view: (key, value) as [B, H, L, D] over the filled rows. An fp8 cache returns
+        dequantised bf16 copies (writing to them does not reach the cache)."""
         B, L, H, D = self.B, self.length, self.H, self.D
+        if self.kv_dtype == "fp8":
+            k, v = ops.kv_dequant_fp8(self.k[layer], self.v[layer], self.k_exp[layer], self.v_exp[layer], rows=L,
+                                      H=H, D=D)
+            return k.view(B, L, H, D).transpose(1, 2), v.view(B, L, H, D).transpose(1, 2)
         return (self.k[layer, :, :L].view(B, L, H, D).transpose(1, 2),
                 self.v[layer, :, :L].view(B, L, H, D).transpose(1, 2))
+
+    def exps(self, layer: int):
+        """the layer's (K, V) exponents [B, Lmax, H] of an fp8 cache; (None, None) otherwise"""
+        return (None, None) if self.k_exp is None else (self.k_exp[layer], self.v_exp[layer])
+
+    def append(self, layer: int, k, v, start, Lnew: int, q_pad=None):
+        """rows k, v [B*Lnew, >= H*D] into the layer's cache at rows start[b] .. (q_pad: a left-padded
+        block, ops.kv_append_ragged), quantised as kv_dtype says"""
+        kc, vc, B = self.k[layer], self.v[layer], self.B
+        if self.kv_dtype == "bf16":
+            if q_pad is None:
+                return ops.kv_append(k, v, kc, vc, start, B=B, Lnew=Lnew)
+            return ops.kv_append_ragged(k, v, kc, vc, start, q_pad, B=B, Lnew=Lnew)
+        kw = dict(B=B, Lnew=Lnew, H=self.H, D=self.D, sim=self.kv_dtype == "fp8_sim")
+        if q_pad is None:
+            return ops.kv_append_fp8(k, v, kc, vc, *self.exps(layer), start, **kw)
+        return ops.kv_append_ragged_fp8(k, v, kc, vc, *self.exps(layer), start, q_pad, **kw)
+
+    def attended(self, layer: int, rows: int):
+        """the layer's (K, V) [B, >= rows, H*D] bf16 as attn_fwd_cached / attn_fwd_ragged read them: the
+        cache itself, or for fp8 its first `rows` rows dequantised into one scratch slab that every
+        layer reuses (stream order: a layer's attention has read it before the next layer's pass writes)"""
+        if self.kv_dtype != "fp8":
+            return self.k[layer], self.v[layer]
+        if self._slab is None or self._slab[0].shape[1] < rows:
+            cap = min(256 * -(-rows // 256), self.max_len)
+            self._slab = tuple(torch.empty((self.B, cap, self.H * self.D), dtype=torch.bfloat16, device=self.k.device)
+                               for _ in range(2))
+        return ops.kv_dequant_fp8(self.k[layer], self.v[layer], self.k_exp[layer], self.v_exp[layer], rows=rows,
+                                  H=self.H, D=self.D, out=self._slab)
 
     def get_seq_length(self) -> int:
         return self.length
 
     def to_legacy_cache(self):
-        """transformers' legacy tuple: ((key, value) [B, H, L, D] per layer), views of this cache"""
+        """transformers' legacy tuple: ((key, value) [B, H, L, D] per layer): views of this cache, or
+        for an fp8 cache dequantised bf16 copies"""
         return tuple(self[i] for i in range(len(self)))
 
     def make_ragged(self):
@@ -197,17 +254,24 @@ class KVCache:
         v = torch.empty_like(k)
         k[:, :, :self.length].copy_(self.k[:, :, :self.length])
         v[:, :, :self.length].copy_(self.v[:, :, :self.length])
+        if self.k_exp is not None:
+            ke = torch.empty((self.k_exp.shape[0], self.B, max_len, self.H), dtype=torch.uint8, device=self.k.device)
+            ve = torch.empty_like(ke)
+            ke[:, :, :self.length].copy_(self.k_exp[:, :, :self.length])
+            ve[:, :, :self.length].copy_(self.v_exp[:, :, :self.length])
+            self.k_exp, self.v_exp = ke, ve
         self.k, self.v, self.max_len = k, v, max_len
 
     @classmethod
-    def from_legacy(cls, legacy, attention_mask=None, extra: int = 256):
+    def from_legacy(cls, legacy, attention_mask=None, extra: int = 256, kv_dtype: str = "bf16"):
         """A transformers-layout cache -- the legacy tuple of per-layer (key, value) [B, H, L, D]
         (what the reference's decode branch indexes, arch_cullavo.py:608-614) or any object with
         to_legacy_cache() (DynamicCache) -- copied into a KVCache with `extra` free rows.
         Attended keys: the reference's rule (:611-632) -- a cached position whose first-layer
         keys are zero is not attended, nor are the
         left-padding positions of the caller's attention_mask -- which must leave one contiguous
-        span per sequence (what the decode kernels read)."""
+        span per sequence (what the decode kernels read). kv_dtype "fp8" / "fp8_sim" quantises the rows
+        on the way in."""
         if hasattr(legacy, "to_legacy_cache"):
             legacy = legacy.to_legacy_cache()
         if not isinstance(legacy, (tuple, list)) or not legacy or len(legacy[0]) != 2:
@@ -215,12 +279,17 @@ class KVCache:
                             f"(key, value) [B, H, L, D]), got {type(legacy).__name__}")
         k0 = legacy[0][0]
         B, H, L, D = k0.shape
-        cache = cls(len(legacy), B, L + extra, H, D, k0.device, dtype=k0.dtype)
+        cache = cls(len(legacy), B, L + extra, H, D, k0.device, dtype=k0.dtype, kv_dtype=kv_dtype)
+        zero = torch.zeros(B, dtype=torch.int32, device=k0.device)
         for i, (k, v) in enumerate(legacy):
             if k.shape != (B, H, L, D) or v.shape != (B, H, L, D):
                 raise ValueError(f"layer {i}: key {tuple(k.shape)} / value {tuple(v.shape)} vs {(B, H, L, D)}")
-            cache.k[i, :, :L].copy_(k.transpose(1, 2).reshape(B, L, H * D))
-            cache.v[i, :, :L].copy_(v.transpose(1, 2).reshape(B, L, H * D))
+            if kv_dtype == "bf16":
+                cache.k[i, :, :L].copy_(k.transpose(1, 2).reshape(B, L, H * D))
+                cache.v[i, :, :L].copy_(v.transpose(1, 2).reshape(B, L, H * D))
+            else:
+                cache.append(i, k.transpose(1, 2).reshape(B * L, H * D), v.transpose(1, 2).reshape(B * L, H * D),
+                             zero, L)
         # a slot is unattended when its first-layer keys are all zero: the reference tests only the
         # head-dim component 0 summed over the heads, which a real key also hits by chance (two
         # bf16 values of opposite sign over 2 heads: seen in the tiny config), so every component
@@ -302,7 +371,7 @@ DECODE_FUSED = "decode_fused"  # one row per sequence: RoPE, append and attentio
 DECODE = "decode"              # one row per sequence: ops.rope_kv_append, then ops.attn_decode
 
 
-def decode_route(dtype) -> str:
+def decode_route(dtype) -> str:  # dtype: the model's rows (a quantised cache decodes bf16 rows)
     """the route of one new row per sequence (FUSE_DECODE_ROPE is read per call: tests patch it)"""
     return DECODE_FUSED if FUSE_DECODE_ROPE and dtype == torch.bfloat16 else DECODE
 
@@ -348,28 +417,48 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, route: str
     kc, vc, pos = cache.k[li], cache.v[li], sctx.position_ids
     rope = dict(head_dim=D, theta=cfg.rope_theta)
     attn = dict(B=B, H=H, D=D, scale=D ** -0.5, kv_start=sctx.kv_start)
+    # the cache's kv_dtype picks the kernels: "fp8" appends codes + exponents and decodes on them,
+    # "fp8_sim" appends the round trip into its bf16 cache and reads it with the bf16 kernels
+    quant = cache.kv_dtype != "bf16"
+    fp8 = dict(sim=cache.kv_dtype == "fp8_sim") if quant else None
+    ke, ve = cache.exps(li)
     if route == PREFILL:
+        # attends the forward's own bf16 k, v (as on a bf16 cache); only the cache write quantises
         ops.rope(q, k, pos, hq=H, hk=H, **rope)
-        ops.kv_append(k, v, kc, vc, start, B=B, Lnew=Lnew)
+        cache.append(li, k, v, start, Lnew)
         o, _ = ops.attn_fwd(q, k, v, Lq=Lnew, Lk=Lnew, causal=True, **attn)
     elif route == CACHED:
         # the new rows against the cached prefix and themselves, causal from the row's own position
+        # (an fp8 cache: against the dequantised slab of its live rows, the new ones included)
         ops.rope(q, k, pos, hq=H, hk=H, **rope)
-        ops.kv_append(k, v, kc, vc, start, B=B, Lnew=Lnew)
-        o, _ = ops.attn_fwd_cached(q, kc, vc, Lq=Lnew, past=cache.length, **attn)
+        cache.append(li, k, v, start, Lnew)
+        ka, va = cache.attended(li, cache.length + Lnew)
+        o, _ = ops.attn_fwd_cached(q, ka, va, Lq=Lnew, past=cache.length, **attn)
     elif route == RAGGED:
         ops.rope(q, k, pos, hq=H, hk=H, **rope)
-        ops.kv_append_ragged(k, v, kc, vc, start, q_pad, B=B, Lnew=Lnew)
-        o, _ = ops.attn_fwd_ragged(q, kc, vc, kv_len, Lq=Lnew, q_pad=q_pad, **attn)
+        cache.append(li, k, v, start, Lnew, q_pad)
+        # every kv_len[b] <= max(lengths) + Lnew, known on the host (no read-back); rows past kv_len[b]
+        # are never attended, whatever their codes dequantise to
+        ka, va = cache.attended(li, min(cache.length + Lnew, cache.max_len))
+        o, _ = ops.attn_fwd_ragged(q, ka, va, kv_len, Lq=Lnew, q_pad=q_pad, **attn)
     elif route == DECODE_FUSED:
-        o = ops.attn_decode_rope(q, k, v, pos, kc, vc, start, max_len=attn_len, theta=cfg.rope_theta, **attn)
+        if quant:
+            o = ops.attn_decode_rope_fp8(q, k, v, pos, kc, vc, ke, ve, start, max_len=attn_len, theta=cfg.rope_theta,
+                                         **attn, **fp8)
+        else:
+            o = ops.attn_decode_rope(q, k, v, pos, kc, vc, start, max_len=attn_len, theta=cfg.rope_theta, **attn)
     elif route == DECODE:
-        if qkv.dtype == torch.bfloat16:  # rotated k goes straight to the cache (one launch for RoPE + append)
+        if quant:
+            ops.rope_kv_append_fp8(q, k, v, pos, kc, vc, ke, ve, start, hq=H, B=B, Lnew=1, **rope, **fp8)
+        elif qkv.dtype == torch.bfloat16:  # rotated k goes straight to the cache (one launch for RoPE + append)
             ops.rope_kv_append(q, k, v, pos, kc, vc, start, hq=H, B=B, Lnew=1, **rope)
         else:
             ops.rope(q, k, pos, hq=H, hk=H, **rope)
             ops.kv_append(k, v, kc, vc, start, B=B, Lnew=1)
-        o = ops.attn_decode(q, kc, vc, kv_len, max_len=attn_len, **attn)
+        if cache.kv_dtype == "fp8":
+            o = ops.attn_decode_fp8(q, kc, vc, ke, ve, kv_len, max_len=attn_len, **attn)
+        else:
+            o = ops.attn_decode(q, kc, vc, kv_len, max_len=attn_len, **attn)
     else:
         raise ValueError(f"layer_infer: unknown attention route {route!r}")
     h2 = _nf4_linear(nf4.get("o"), o, layer.self_attn.o_proj.weight, lg["o"], residual=h, gemv=gemv)
@@ -543,6 +632,8 @@ class DecodeGraph:
         # for the graph's lifetime even if quant.nf4_weights() drops them from the layers meanwhile
         from .quant import nf4_weights
         self.nf4_refs = [nf4_weights(layer) for layer in lm.model.layers] if NF4_DECODE else []
+        # and into the cache's storage (an fp8 cache: codes and exponents): a grow() meanwhile must not free it
+        self.kv_refs = (cache.k, cache.v, cache.k_exp, cache.v_exp)
         # adapters: the captured products read lora_A / lora_B (FUSE_DECODE_LORA: in their epilogues, the
         # same route as the eager step, decided by layer_infer at capture) straight from the LoRA arena,
         # whose storage the model owns and never reallocates: it outlives the graph, and a replay after a
@@ -571,7 +662,7 @@ class DecodeGraph:
             self.live.copy_(self.sampler.finished == 0)
         h = self.embed(self.ids[:, None]).reshape(B, lm.cfg.hidden_size)
         sctx = StepContext(B, 1, self.pos[:, None], cache.kv_start, lora_seed=0)
-        logits = run_chunk(lm, h, sctx, cache, decode_route(cache.k.dtype), self.start, attn_len=cache.max_len)
+        logits = run_chunk(lm, h, sctx, cache, decode_route(h.dtype), self.start, attn_len=cache.max_len)
         if self.sampler is not None:  # the next step's token, written where this graph's embedding reads it
             self.sampler.sample(logits)
         n = self.live if self.live is not None else 1
@@ -703,18 +794,20 @@ def _infer_ragged(lm, embeds, q_pad, position_ids, cache: KVCache, prefill_chunk
 
 
 def lm_infer(lm, embeds, attention_mask, position_ids, cache: KVCache | None, max_len: int,
-             prefill_chunk: int | None = None):
+             prefill_chunk: int | None = None, kv_dtype: str = "bf16"):
     """LlamaForCausalLM with a KV cache: prefill (cache None or empty), one decode step, or a
     continuation of Lnew > 1 new tokens per sequence on a filled cache (a follow-up turn, a second
     question about the cached image, the later pieces of a chunked prefill). prefill_chunk: run the
     rows in pieces of at most that many per sequence (None: one pass). Returns (logits [B, Lnew, V]
-    bf16, cache)."""
+    bf16, cache). kv_dtype: the format of the cache created here when `cache` is None (an existing
+    cache keeps its own)."""
     B, Lnew, d = embeds.shape
     cfg = lm.cfg
     if embeds.dtype != torch.bfloat16:
         raise NotImplementedError("KV-cache decode runs on the bf16 model (the f32 mode is a parity mode)")
     if cache is None:
-        cache = KVCache(cfg.num_hidden_layers, B, max_len, cfg.num_attention_heads, cfg.head_dim, embeds.device)
+        cache = KVCache(cfg.num_hidden_layers, B, max_len, cfg.num_attention_heads, cfg.head_dim, embeds.device,
+                        kv_dtype=kv_dtype)
     prefill = cache.length == 0
     if prefill:
         if Lnew > cache.max_len:  # kv_append writes rows [0, Lnew) of every sequence's cache

@@ -23,6 +23,8 @@ __all__ = [
     "im2col_patches", "vision_embed_ln", "merge_plan", "row_gather2", "shift_targets", "ce_fwd",
     "ce_reduce", "ce_bwd", "adamw", "sumsq", "clip_coef", "scale_inplace", "kv_append", "attn_decode",
     "kv_append_ragged", "attn_fwd_ragged",
+    "kv_append_fp8", "kv_append_ragged_fp8", "rope_kv_append_fp8", "attn_decode_fp8", "attn_decode_rope_fp8",
+    "kv_dequant_fp8",
     "clip_image_preprocess", "visimage_geometry", "draw_boxes",
     "nf4_quantize", "nf4_dequantize", "nf4_decode_linear", "sample_token",
 ]
@@ -700,6 +702,148 @@ def attn_decode(q, k_cache, v_cache, kv_len, *, B: int, H: int, D: int, max_len:
     call("attn_decode", _ptr(q), _ld(q), _ptr(k_cache), _ptr(v_cache), k_cache.stride(1), k_cache.stride(0),
          _ptr(kv_len), _ptr(kv_start), _ptr(o), _ld(o), B, H, max_len, D, float(scale), _ptr(ws), _stream())
     return o
+
+
+# ---- FP8 KV cache (INTEGRATION.md "FP8 KV cache") ----------------------------------------------
+def _fp8_cache_args(name: str, k_cache, v_cache, k_exp, v_exp, B: int, H: int, D: int, sim: bool):
+    """The cache arguments of the FP8 entry points, validated: codes uint8 [B, Lmax, H*D] with
+    exponents uint8 [B, Lmax, H], or sim: a bf16 cache [B, Lmax, H*D] that receives the dequantised
+    values (no exponents). Returns (k ptr, v ptr, ld_tok, ld_batch, k_exp ptr, v_exp ptr, ld_etok, ld_ebatch)."""
+    want = torch.bfloat16 if sim else torch.uint8
+    if k_cache.dtype != want or v_cache.dtype != want:
+        raise TypeError(f"{name}: expected {want} caches ({'the round-trip twin' if sim else 'e4m3 codes'}), got "
+                        f"{k_cache.dtype} / {v_cache.dtype}")
+    if (k_cache.dim() != 3 or k_cache.stride(2) != 1 or v_cache.stride() != k_cache.stride()
+            or k_cache.shape != v_cache.shape or k_cache.shape[0] != B or k_cache.shape[2] != H * D):
+        raise ValueError(f"{name}: expected caches [{B}, Lmax, {H * D}] with unit column stride and the same strides, "
+                         f"got {tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
+    if D != 128:
+        raise NotImplementedError(f"{name}: the FP8 KV cache is built for head_dim 128, got {D}")
+    if sim:
+        return _ptr(k_cache), _ptr(v_cache), k_cache.stride(1), k_cache.stride(0), None, None, 0, 0
+    if k_exp is None or v_exp is None:
+        raise ValueError(f"{name}: an FP8 cache needs its exponents (k_exp, v_exp)")
+    _dev(k_exp, v_exp)
+    L = k_cache.shape[1]
+    for e in (k_exp, v_exp):
+        if e.dtype != torch.uint8 or e.shape != (B, L, H) or e.stride(2) != 1 or e.stride() != k_exp.stride():
+            raise ValueError(f"{name}: expected exponents uint8 [{B}, {L}, {H}] with unit column stride, got "
+                             f"{e.dtype} {tuple(e.shape)}")
+    return (_ptr(k_cache), _ptr(v_cache), k_cache.stride(1), k_cache.stride(0), _ptr(k_exp), _ptr(v_exp),
+            k_exp.stride(1), k_exp.stride(0))
+
+
+def _bf16_rows(name: str, H: int, D: int, **rows):
+    for n, t in rows.items():
+        if t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[1] < H * D:
+            raise TypeError(f"{name}: {n} must be bf16 [rows, >= {H * D}], got {t.dtype} {tuple(t.shape)}")
+
+
+def kv_append_fp8(k, v, k_cache, v_cache, k_exp, v_exp, start, *, B: int, Lnew: int, H: int, D: int,
+                  sim: bool = False):
+    """cullavo_kv_append_fp8: kv_append with quantisation. k, v bf16 [B*Lnew, >= H*D]; caches: e4m3 codes
+    uint8 [B, Lmax, H*D] with exponents uint8 [B, Lmax, H] (one per token and head, e + 127). sim: the
+    caches are bf16 and receive the dequantised values (k_exp, v_exp unused)."""
+    _dev(k, v, k_cache, v_cache, start)
+    _bf16_rows("kv_append_fp8", H, D, k=k, v=v)
+    _int32_rows("start", start, B)
+    if k.shape[0] != B * Lnew or v.shape[0] != B * Lnew:
+        raise ValueError(f"kv_append_fp8: k {tuple(k.shape)} / v {tuple(v.shape)} vs B {B}, Lnew {Lnew}")
+    c = _fp8_cache_args("kv_append_fp8", k_cache, v_cache, k_exp, v_exp, B, H, D, sim)
+    call("kv_append_fp8", _ptr(k), _ld(k), _ptr(v), _ld(v), *c, _ptr(start), B, Lnew, H, D, int(sim), _stream())
+
+
+def kv_append_ragged_fp8(k, v, k_cache, v_cache, k_exp, v_exp, start, q_pad, *, B: int, Lnew: int, H: int, D: int,
+                         sim: bool = False):
+    """cullavo_kv_append_ragged_fp8: kv_append_ragged with quantisation (kv_append_fp8's arguments plus
+    q_pad int32 [B]: sequence b's leading padding rows, which are not written)."""
+    _dev(k, v, k_cache, v_cache, start, q_pad)
+    _bf16_rows("kv_append_ragged_fp8", H, D, k=k, v=v)
+    _int32_rows("start", start, B)
+    _int32_rows("q_pad", q_pad, B)
+    if k.shape[0] != B * Lnew or v.shape[0] != B * Lnew:
+        raise ValueError(f"kv_append_ragged_fp8: k {tuple(k.shape)} / v {tuple(v.shape)} vs B {B}, Lnew {Lnew}")
+    c = _fp8_cache_args("kv_append_ragged_fp8", k_cache, v_cache, k_exp, v_exp, B, H, D, sim)
+    call("kv_append_ragged_fp8", _ptr(k), _ld(k), _ptr(v), _ld(v), *c, _ptr(start), _ptr(q_pad), B, Lnew, H, D,
+         int(sim), _stream())
+
+
+def rope_kv_append_fp8(q, k, v, position_ids, k_cache, v_cache, k_exp, v_exp, start, *, hq: int, head_dim: int,
+                       theta: float, B: int, Lnew: int, sim: bool = False):
+    """cullavo_rope_kv_append_fp8: rope(q, k) in place on q, the ROTATED k and v quantised into the
+    caches (k itself is left unrotated); bitwise rope() + kv_append_fp8()."""
+    _dev(q, k, v, position_ids, k_cache, v_cache, start)
+    H = k_cache.shape[-1] // head_dim
+    _bf16_rows("rope_kv_append_fp8", H, head_dim, k=k, v=v)
+    _bf16_rows("rope_kv_append_fp8", hq, head_dim, q=q)
+    _int32_rows("start", start, B)
+    if q.shape[0] != B * Lnew or k.shape[0] != B * Lnew or v.shape[0] != B * Lnew:
+        raise ValueError(f"rope_kv_append_fp8: q / k / v rows vs B {B}, Lnew {Lnew}")
+    c = _fp8_cache_args("rope_kv_append_fp8", k_cache, v_cache, k_exp, v_exp, B, H, head_dim, sim)
+    call("rope_kv_append_fp8", _ptr(q), _ld(q), _ptr(k), _ld(k), _ptr(v), _ld(v), _ptr(position_ids), B * Lnew, hq, H,
+         head_dim, float(theta), *c, _ptr(start), Lnew, int(sim), _stream())
+
+
+def attn_decode_fp8(q, k_cache, v_cache, k_exp, v_exp, kv_len, *, B: int, H: int, D: int, max_len: int, scale: float,
+                    kv_start=None, out=None):
+    """cullavo_attn_decode_fp8: attn_decode on an FP8 cache (codes + exponents); bitwise attn_decode on
+    kv_dequant_fp8 of the same cache. No V row or exponent below kv_start[b] is read."""
+    _dev(q, k_cache, v_cache, kv_len, kv_start)
+    _bf16_rows("attn_decode_fp8", H, D, q=q)
+    _int32_rows("kv_len", kv_len, B)
+    if kv_start is not None:
+        _int32_rows("kv_start", kv_start, B)
+    c = _fp8_cache_args("attn_decode_fp8", k_cache, v_cache, k_exp, v_exp, B, H, D, False)
+    o = out if out is not None else torch.empty((B, H * D), dtype=q.dtype, device=q.device)
+    nbytes = lib().cullavo_attn_decode_workspace(B, H, max_len, D)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
+    call("attn_decode_fp8", _ptr(q), _ld(q), *c, _ptr(kv_len), _ptr(kv_start), _ptr(o), _ld(o), B, H, max_len, D,
+         float(scale), _ptr(ws), _stream())
+    return o
+
+
+def attn_decode_rope_fp8(q, k, v, position_ids, k_cache, v_cache, k_exp, v_exp, start, *, B: int, H: int, D: int,
+                         max_len: int, scale: float, theta: float, kv_start=None, out=None, sim: bool = False):
+    """cullavo_attn_decode_rope_fp8: attn_decode_rope on an FP8 cache -- the new row is rotated,
+    quantised (codes and exponents written to row start[b]) and attended as dequantised; bitwise
+    rope_kv_append_fp8 (Lnew = 1) + attn_decode_fp8. sim: a bf16 cache that receives the dequantised row."""
+    _dev(q, k, v, position_ids, k_cache, v_cache, start, kv_start)
+    _bf16_rows("attn_decode_rope_fp8", H, D, q=q, k=k, v=v)
+    _int32_rows("start", start, B)
+    if kv_start is not None:
+        _int32_rows("kv_start", kv_start, B)
+    c = _fp8_cache_args("attn_decode_rope_fp8", k_cache, v_cache, k_exp, v_exp, B, H, D, sim)
+    o = out if out is not None else torch.empty((B, H * D), dtype=q.dtype, device=q.device)
+    nbytes = lib().cullavo_attn_decode_workspace(B, H, max_len, D)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
+    call("attn_decode_rope_fp8", _ptr(q), _ld(q), _ptr(k), _ld(k), _ptr(v), _ld(v), _ptr(position_ids), float(theta),
+         *c, _ptr(start), _ptr(kv_start), _ptr(o), _ld(o), B, H, max_len, D, float(scale), int(sim), _ptr(ws),
+         _stream())
+    return o
+
+
+def kv_dequant_fp8(k_cache, v_cache, k_exp, v_exp, *, rows: int, H: int, D: int, out=None):
+    """cullavo_kv_dequant_fp8: rows [0, rows) of every sequence's codes and exponents to bf16, exact.
+    Returns (k, v) bf16 [B, rows, H*D]; out: a pair of bf16 [B, >= rows, H*D] slabs to write into (their
+    first `rows` rows are returned)."""
+    B = k_cache.shape[0]
+    _dev(k_cache, v_cache)
+    c = _fp8_cache_args("kv_dequant_fp8", k_cache, v_cache, k_exp, v_exp, B, H, D, False)
+    if not 0 <= rows <= k_cache.shape[1]:
+        raise ValueError(f"kv_dequant_fp8: rows {rows} of a cache of {k_cache.shape[1]}")
+    if out is None:
+        ko = torch.empty((B, rows, H * D), dtype=torch.bfloat16, device=k_cache.device)
+        vo = torch.empty_like(ko)
+    else:
+        ko, vo = out
+        _dev(ko, vo)
+        for t in (ko, vo):
+            if (t.dtype != torch.bfloat16 or t.dim() != 3 or t.shape[0] != B or t.shape[1] < rows
+                    or t.shape[2] != H * D or t.stride(2) != 1 or t.stride() != ko.stride()):
+                raise ValueError(f"kv_dequant_fp8: out must be two bf16 [{B}, >= {rows}, {H * D}] slabs of the same "
+                                 f"strides, got {t.dtype} {tuple(t.shape)}")
+    call("kv_dequant_fp8", *c, _ptr(ko), _ptr(vo), ko.stride(1), ko.stride(0), B, rows, H, D, _stream())
+    return ko[:, :rows], vo[:, :rows]
 
 
 def attn_fwd_cached(q, k_cache, v_cache, *, B: int, H: int, Lq: int, past: int, D: int, scale: float,

@@ -65,7 +65,9 @@ extern "C" {
    (the ragged KV cache: two new entry points, nothing existing touched), and cullavo_attn_fwd_varlen,
    cullavo_attn_bwd_varlen and cullavo_attn_varlen_set_check (packed training sequences), and
    cullavo_decode_linear_lora and cullavo_nf4_decode_linear_lora (the decode products with the LoRA
-   up-projection in their epilogue). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
+   up-projection in their epilogue), and the FP8 KV cache's six entry points (cullavo_kv_append_fp8,
+   cullavo_kv_append_ragged_fp8, cullavo_rope_kv_append_fp8, cullavo_attn_decode_fp8,
+   cullavo_attn_decode_rope_fp8, cullavo_kv_dequant_fp8). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
 #define CULLAVO_ABI_VERSION 9
 
 int cullavo_abi_version(void);
@@ -534,6 +536,69 @@ size_t cullavo_attn_decode_workspace(int B, int H, int max_len, int D);
 int cullavo_attn_decode(const void* q, int64_t ldq, const void* k_cache, const void* v_cache, int64_t ld_tok,
                         int64_t ld_batch, const int32_t* kv_len, const int32_t* kv_start, void* o, int64_t ldo,
                         int B, int H, int max_len, int D, float scale, float* workspace, void* stream);
+
+/* ---- FP8 KV cache (added under ABI 9, additive: six new entry points, nothing existing touched) ---
+ * Format (INTEGRATION.md "FP8 KV cache"). Per layer the K and V codes are uint8 [B, Lmax, H*D] in
+ * OCP e4m3fn (token stride ld_tok, batch stride ld_batch, in bytes) and the K and V exponents uint8
+ * [B, Lmax, H] (strides ld_etok, ld_ebatch), one per token and head, holding e + 127. e is the
+ * smallest integer with amax * 2^-e <= 448 (amax: the head row's max |x| over its D bf16 values),
+ * clamped to e >= -100; code = e4m3 round-to-nearest-even of x * 2^-e; the value a code stands for is
+ * f32(code) * 2^e, always a bf16 number. Non-finite inputs are out of scope, as for the bf16 cache.
+ * D must be 128 (CULLAVO_EUNSUPPORTED otherwise). Argument errors (CULLAVO_EINVAL) come before any
+ * launch: null exponents, code pointers or rows not 16-byte aligned, bf16 rows not 16-byte aligned.
+ * No allocation, stream order, plain pointers, as everywhere in this header.
+ *
+ * sim != 0 (the "fp8_sim" twin, on the calls that take it): k_codes / v_codes are a BF16 cache (strides
+ * in bf16 elements, as cullavo_kv_append takes them) that receives the dequantised values -- quantise,
+ * then dequantise, in the append; the exponents are not written and may be null. Every later read of
+ * that cache is a plain bf16 one. */
+/* cullavo_kv_append with quantisation: rows start[b] .. start[b] + Lnew - 1 of sequence b get the
+ * codes and exponents of k / v rows [B*Lnew, H*D] bf16 (row strides ldk, ldv); no other row, code or
+ * exponent is written. */
+int cullavo_kv_append_fp8(const void* k, int64_t ldk, const void* v, int64_t ldv, void* k_codes, void* v_codes,
+                          int64_t ld_tok, int64_t ld_batch, void* k_exp, void* v_exp, int64_t ld_etok,
+                          int64_t ld_ebatch, const int32_t* start, int B, int Lnew, int H, int D, int sim,
+                          void* stream);
+/* cullavo_kv_append_ragged with quantisation: the q_pad[b] leading padding rows of sequence b are not
+ * written, the others go to row start[b] + t - q_pad[b]. */
+int cullavo_kv_append_ragged_fp8(const void* k, int64_t ldk, const void* v, int64_t ldv, void* k_codes,
+                                 void* v_codes, int64_t ld_tok, int64_t ld_batch, void* k_exp, void* v_exp,
+                                 int64_t ld_etok, int64_t ld_ebatch, const int32_t* start, const int32_t* q_pad,
+                                 int B, int Lnew, int H, int D, int sim, void* stream);
+/* cullavo_rope_kv_append with quantisation: q rotated in place, the ROTATED key quantised (k itself
+ * is left as it was) -- bitwise cullavo_rope followed by cullavo_kv_append_fp8. */
+int cullavo_rope_kv_append_fp8(void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                               const int64_t* position_ids, int64_t tokens, int hq, int hk, int head_dim,
+                               float theta, void* k_codes, void* v_codes, int64_t ld_tok, int64_t ld_batch,
+                               void* k_exp, void* v_exp, int64_t ld_etok, int64_t ld_ebatch,
+                               const int32_t* start, int Lnew, int sim, void* stream);
+/* cullavo_attn_decode on codes: the same 64-key chunks, partials, combine kernel, kv_start rule (no V
+ * row or exponent below kv_start[b] is read) and reduction order; a key's scale multiplies its finished
+ * score once and a value's scale its probability once. Bitwise cullavo_attn_decode on the
+ * cullavo_kv_dequant_fp8 image of the same cache. Workspace: cullavo_attn_decode_workspace bytes. */
+int cullavo_attn_decode_fp8(const void* q, int64_t ldq, const void* k_codes, const void* v_codes, int64_t ld_tok,
+                            int64_t ld_batch, const void* k_exp, const void* v_exp, int64_t ld_etok,
+                            int64_t ld_ebatch, const int32_t* kv_len, const int32_t* kv_start, void* o,
+                            int64_t ldo, int B, int H, int max_len, int D, float scale, float* workspace,
+                            void* stream);
+/* cullavo_attn_decode_rope on an FP8 cache: bitwise cullavo_rope_kv_append_fp8 (Lnew = 1) followed by
+ * cullavo_attn_decode_fp8 with kv_len = start + 1. The workgroup that owns row start[b] rotates the key,
+ * reduces amax over the head for K and V, writes codes and exponents and attends the DEQUANTISED new
+ * row, so the step sees what every later step reads. sim != 0: a bf16 cache receiving the dequantised
+ * row, the rest cullavo_attn_decode_rope. */
+int cullavo_attn_decode_rope_fp8(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                 int64_t ldv, const int64_t* position_ids, float theta, void* k_codes,
+                                 void* v_codes, int64_t ld_tok, int64_t ld_batch, void* k_exp, void* v_exp,
+                                 int64_t ld_etok, int64_t ld_ebatch, const int32_t* start,
+                                 const int32_t* kv_start, void* o, int64_t ldo, int B, int H, int max_len, int D,
+                                 float scale, int sim, float* workspace, void* stream);
+/* Rows [0, rows) of every sequence's K and V codes to bf16 slabs k_out, v_out [B, rows, H*D] (strides
+ * ld_otok, ld_obatch in elements), exact: what the multi-token routes (cullavo_attn_fwd_cached /
+ * cullavo_attn_fwd_ragged) attend on an FP8 cache. Replaces nothing: the bf16 cache needs no such pass. */
+int cullavo_kv_dequant_fp8(const void* k_codes, const void* v_codes, int64_t ld_tok, int64_t ld_batch,
+                           const void* k_exp, const void* v_exp, int64_t ld_etok, int64_t ld_ebatch, void* k_out,
+                           void* v_out, int64_t ld_otok, int64_t ld_obatch, int B, int rows, int H, int D,
+                           void* stream);
 
 /* ---- token sampling (generate; added under ABI 8) ---------------------------------------------
  * Replaces HF's logits warpers and multinomial behind the reference's
