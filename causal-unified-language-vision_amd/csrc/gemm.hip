@@ -790,6 +790,9 @@ static int gemm_impl(const cullavo_gemm_desc& d, void* stream, int tile_hint) {
   CV_REQUIRE(d.drop_operand >= 0 && d.drop_operand <= 3, CULLAVO_EINVAL, "drop_operand");
   CV_REQUIRE(d.drop_operand == 0 || (d.drop_p >= 0.f && d.drop_p < 1.f), CULLAVO_EINVAL, "drop_p must be in [0, 1)");
   CV_REQUIRE(d.drop_operand != 1 || a_layout == 0, CULLAVO_EUNSUPPORTED, "dropout on A needs a_layout 0");
+  // bf16 mode 1 has the (0,0) kernel only: a [K, N] B would be read as [N, K] (gemm_f32_k takes both)
+  CV_REQUIRE(d.drop_operand != 1 || b_layout == 0 || d.f32_operands, CULLAVO_EUNSUPPORTED,
+             "dropout on A needs b_layout 0 with bf16 operands");
   CV_REQUIRE(d.drop_operand != 2 || b_layout == 1, CULLAVO_EUNSUPPORTED, "dropout on B needs b_layout 1");
   CV_REQUIRE(d.lora_u == nullptr || !d.f32_operands, CULLAVO_EUNSUPPORTED, "fused LoRA: bf16 operands only");
   if (d.f32_operands) return cullavo_gemm_f32_impl(d, CV_STREAM(stream));  // gemm_f32.hip

@@ -98,7 +98,8 @@ int cullavo_gemm(int a_layout, int b_layout, int64_t M, int64_t N, int64_t K,
  *   addend [M, N] bf16 (ld_addend, multiple of 4, nullable): added after the bias with the
  *           module chain's roundings, v = round(round(alpha*A.B^T + bias) + addend), before
  *           preact / activation / residual;
- *   drop_operand: 0 none; 1 dropout on A (needs a_layout 0, A[m][k] = x[token m][feature k]);
+ *   drop_operand: 0 none; 1 dropout on A (needs a_layout 0, A[m][k] = x[token m][feature k], and with
+ *           bf16 operands b_layout 0: any other call returns CULLAVO_EUNSUPPORTED before a launch);
  *           2 on B (needs b_layout 1, B[k][n] = x[token k][feature n]); 3 on the output
  *           (token m, feature n), applied to alpha*A.B^T before bias / beta;
  *   drop_p in [0, 1), drop_seed: one hash(seed, token, feature / 2) per feature pair; element

@@ -165,20 +165,24 @@ def g1_ok(c32, ref, absprod, K, alpha=1.0):
 # G2
 # ---------------------------------------------------------------------------------------------
 def chain_replay(c32, alpha=1.0, bias=None, addend=None, want_preact=False, rounds=False, residual=None,
-                 beta=0.0, old=None, out_dtype=BF):
+                 beta=0.0, old=None, out_dtype=BF, keep=None, drop_scale=1.0):
     """store4 / store8 (gemm_common.h) on the kernel's own f32 plain product, in torch f32:
-      v = alpha * c; v += bias; v = bf16(v) + addend; with a pre-activation output or an activation
-      (`rounds`) v = bf16(v), stored as the pre-activation; v = bf16(v) + residual; v += beta * old;
-      stored as bf16 or f32.
+      v = alpha * c; with output dropout (drop_operand 3: `keep` bool [M, N], `drop_scale` 1 / (1 - p))
+      v = keep ? v * drop_scale : 0; v += bias; v = bf16(v) + addend; with a pre-activation output or
+      an activation (`rounds`) v = bf16(v), stored as the pre-activation; v = bf16(v) + residual;
+      v += beta * old; stored as bf16 or f32.
     Every step is one f32 multiply or add or one bf16 rounding, so this is bit for bit what the
-    kernel stores PROVIDED alpha and beta are powers of two (the cases use alpha in {1, 2, 0.5} and
-    beta in {1, 0.5} only): alpha * c and beta * old are then exact, and the replay is the same
-    whether or not the compiler contracts acc * alpha + bias or v + beta * old into one fma.
+    kernel stores PROVIDED alpha, beta and the dropout scale are powers of two (the cases use alpha in
+    {1, 2, 0.5}, beta in {1, 0.5} and p = 0.5 only): alpha * c, v * drop_scale and beta * old are then
+    exact, and the replay is the same whether or not the compiler contracts acc * alpha + bias,
+    v * drop_scale + bias or v + beta * old into one fma.
     Returns (out, pre-activation or None), the value after the `rounds` step left in f32 when an
     activation follows (the caller applies it)."""
-    for s in (alpha, beta):
+    for s in (alpha, beta, drop_scale):
         assert s == 0.0 or math.frexp(abs(s))[0] == 0.5, "powers of two only"
     v = c32.float() * alpha
+    if keep is not None:
+        v = torch.where(keep, v * drop_scale, torch.zeros_like(v))
     if bias is not None:
         v = v + bias.float()
     if addend is not None:

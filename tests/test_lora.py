@@ -9,6 +9,8 @@ Tolerances: bf16 storage (2^-8 relative step). Kernel-level outputs max|err| <= 
 model-level (bf16, against the bf16-faithful peft restatement) logits relative-L2 <= 1e-2, loss
 |d| <= 1e-2, every trainable gradient relative-L2 <= 2e-2 (as tests/test_model_gpu.py); the f32
 parity mode at 1e-3 logits / 1e-4 loss / 1e-3 gradients.
+The bf16 GEMM's dropout modes and lora_dx_k are held per element by tests/test_lora_drop_accuracy_gpu.py
+(gates in tests/lora_drop_refs.py, proven on the CPU by tests/test_lora_drop_refs_host.py).
 """
 import numpy as np
 import pytest
