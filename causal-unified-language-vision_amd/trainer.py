@@ -60,7 +60,18 @@ class Accel:
         self.reducer: GradReducer | None = None
 
     def backward(self, loss):
-        loss.backward()
+        """accelerate's Accelerator.backward (the reference calls it on an
+        Accelerator(gradient_accumulation_steps=GRAD_CUM), trainer/distributed_trainer.py:15) divides
+        before it differentiates: `loss = loss / self.gradient_accumulation_steps`, so a cycle
+        accumulates the mean of its micro-batches' gradients and GRAD_MAX clips that mean. Here the
+        factor enters as the backward's seed gradient: a device fill, no host sync; a power of two
+        scales every bf16 intermediate exactly. With one micro-batch per cycle the call is the plain
+        loss.backward() it always was."""
+        n = self.gradient_accumulation_steps
+        if n == 1:
+            loss.backward()
+        else:
+            loss.backward(gradient=torch.full_like(loss, 1.0 / n))
         if self.sync_gradients and self.reducer is not None:
             self.reducer.finish()
 
