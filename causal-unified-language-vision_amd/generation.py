@@ -84,6 +84,31 @@ FUSE_DECODE_LORA = "lora" in _FUSE
 # CULLAVO_NF4_DECODE=0: a model quantised by quant.quantize_lm_nf4_ decodes through the bf16 GEMV on
 # its (dequantised) arena weights instead of the 4-bit product on the NF4 copies (A/B switch)
 NF4_DECODE = os.environ.get("CULLAVO_NF4_DECODE", "1") != "0"
+# CULLAVO_DECODE_WIDE=1: a one-token step at 17 .. 64 sequences runs its Linears on the wide
+# weight-streaming product (cullavo_decode_linear_wide) wherever ops.WIDE_TILES_FASTER does not keep the
+# shape on ops.linear's tiles. Off by default: on the 7B products the tiles' split-K route already
+# streams the weights at 1.9-3.8 TB/s and the wide product beat it only on o up to 32 rows and on
+# gate|up and lm_head at 17, so the replayed 7B step measured 0.992 of the tiles' time at batch 32
+# (8.120 against 8.183 ms per token, the tiles' own runs spread 0.5 %) and 1.000 at 64, where every
+# product stays on the tiles (INTEGRATION.md "Wide decode steps"; profiles/r21/wide_decode/)
+DECODE_WIDE = os.environ.get("CULLAVO_DECODE_WIDE", "0") == "1"
+
+
+def wide_route(B: int, Lnew: int, dtype, switch: bool | None = None) -> bool:
+    """Whether a step of Lnew new rows for each of B sequences runs its Linears on the wide
+    weight-streaming product (ops.decode_linear_wide): one token per sequence, bf16 rows, 17 <= B <= 64,
+    and the switch on (None: DECODE_WIDE, read per call: tests patch it). Everything else keeps its
+    route: B <= 16 the GEMV, multi-token steps and the f32 parity model the tiles."""
+    if switch is None:
+        switch = DECODE_WIDE
+    return bool(switch) and Lnew == 1 and dtype == torch.bfloat16 and ops.WIDE_M_MIN <= B <= ops.WIDE_M_MAX
+
+
+def _wide_takes(w, M: int) -> bool:
+    """a weight the wide product takes at M rows: its shape rules, and not a measured loser
+    (ops.WIDE_TILES_FASTER), which stays on the tiles"""
+    rows, K = w.shape
+    return rows % 8 == 0 and K % 8 == 0 and not ops.wide_prefers_tiles(rows, K, M)
 
 
 def left_pad_span(mask, message: str):
@@ -333,17 +358,20 @@ def _decode_lora(t, M: int, rows: int):
     return t.decode_args(M, rows)
 
 
-def _nf4_linear(q, x, w, group, residual=None, gemv: bool = False):
+def _nf4_linear(q, x, w, group, residual=None, gemv: bool = False, wide: bool = False):
     """One Linear of the decode step: on the NF4 copy q = (codes, absmax) when the layer has one
     (w goes along, so a shape on which the bf16 GEMV measured faster stays there,
     ops.NF4_BF16_FASTER), else on w. gemv: these are decode rows. The group's LoRA term rides in the
     product's epilogue (_decode_lora; ops.nf4_decode_linear takes the LoraTerm itself and decides the
-    same way) or, where it cannot, is materialised and passed as the epilogue addend."""
+    same way) or, where it cannot, is materialised and passed as the epilogue addend. wide: the rows
+    of a wide step (wide_route): the wide product, the term materialised as its addend."""
     t, _ = group.forward(x, False, 0)
     if q is None:
         la = _decode_lora(t, x.shape[0], w.shape[0]) if gemv else None
         if la is not None:
             return ops.decode_linear(x, w, residual=residual, lora=la)
+        if wide and _wide_takes(w, x.shape[0]):
+            return ops.decode_linear_wide(x, w, residual=residual, addend=t)
         return ops.linear(x, w, residual=residual, addend=t)
     if t is not None and not FUSE_DECODE_LORA:
         t = t.materialize()
@@ -389,6 +417,9 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, route: str
     B, Lnew = sctx.B, sctx.L
     # the decode rows: one per sequence, few enough for the weight-streaming products
     gemv = Lnew == 1 and h.shape[0] <= 16 and h.dtype == torch.bfloat16
+    # 17 .. 64 of them: the wide weight-streaming products (NF4 copies are not read above 16 rows: the
+    # arena's dequantised bf16 weights, as before)
+    wide = wide_route(B, Lnew, h.dtype)
     # the layer's NF4 weight copies (quant.quantize_lm_nf4_; empty: none, or stale and dropped): the
     # decode rows' products stream 4.5 bits per weight (cullavo_nf4_decode_linear), whatever
     # FUSE_DECODE_NORMS / FUSE_DECODE_SWIGLU say; a weight left bf16 (K % 64 != 0) takes ops.linear
@@ -412,7 +443,7 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, route: str
                                 lora=_norm_lora(lg["qkv"], h, norm1["norm_w"], norm1["eps"], 3 * d))
     else:
         x1, _ = ops.rmsnorm_fwd(h, layer.input_layernorm.weight, cfg.rms_norm_eps)
-        qkv = _nf4_linear(nf4.get("qkv"), x1, layer.w_qkv(), lg["qkv"], gemv=gemv)
+        qkv = _nf4_linear(nf4.get("qkv"), x1, layer.w_qkv(), lg["qkv"], gemv=gemv, wide=wide)
     q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
     kc, vc, pos = cache.k[li], cache.v[li], sctx.position_ids
     rope = dict(head_dim=D, theta=cfg.rope_theta)
@@ -461,7 +492,7 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, route: str
             o = ops.attn_decode(q, kc, vc, kv_len, max_len=attn_len, **attn)
     else:
         raise ValueError(f"layer_infer: unknown attention route {route!r}")
-    h2 = _nf4_linear(nf4.get("o"), o, layer.self_attn.o_proj.weight, lg["o"], residual=h, gemv=gemv)
+    h2 = _nf4_linear(nf4.get("o"), o, layer.self_attn.o_proj.weight, lg["o"], residual=h, gemv=gemv, wide=wide)
     w_gu, w_down = layer.w_gu(), layer.mlp.down_proj.weight
     F2 = w_gu.shape[0]
     if fused:
@@ -497,9 +528,16 @@ def layer_infer(layer, h, sctx: StepContext, cache: KVCache, li: int, route: str
                                                      addend=t if FUSE_DECODE_LORA else t.materialize()))
     elif la is not None:
         a = ops.swiglu_fwd(ops.decode_linear(x2, w_gu, lora=la))
+    elif wide and F2 % 16 == 0 and _wide_takes(w_gu, M):
+        # the wide product with the SwiGLU in its epilogue; adapters: their term as the addend of the
+        # plain product, then the SwiGLU's own launch
+        if t is None and FUSE_DECODE_GU:
+            a = ops.decode_linear_wide(x2, w_gu, transform=3)
+        else:
+            a = ops.swiglu_fwd(ops.decode_linear_wide(x2, w_gu, addend=t))
     else:
         a = ops.swiglu_fwd(ops.linear(x2, w_gu, addend=t))
-    return _nf4_linear(nf4.get("down"), a, w_down, lg["down"], residual=h2, gemv=gemv)
+    return _nf4_linear(nf4.get("down"), a, w_down, lg["down"], residual=h2, gemv=gemv, wide=wide)
 
 
 SAMPLE_TOP_K_MAX = 1024  # cullavo_sample_token: 1 <= top_k <= 1024
@@ -739,6 +777,8 @@ def run_chunk(lm, h, sctx: StepContext, cache: KVCache, route: str, start, q_pad
     for li, layer in enumerate(lm.model.layers):
         h = layer_infer(layer, h, sctx, cache, li, route, start, kv_len, q_pad, attn_len)
     x, _ = ops.rmsnorm_fwd(h, lm.model.norm.weight, lm.cfg.rms_norm_eps)
+    if wide_route(sctx.B, sctx.L, x.dtype) and _wide_takes(lm.lm_head.weight, x.shape[0]):
+        return ops.decode_linear_wide(x, lm.lm_head.weight)
     return ops.linear(x, lm.lm_head.weight)
 
 

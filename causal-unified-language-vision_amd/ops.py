@@ -27,6 +27,7 @@ __all__ = [
     "kv_dequant_fp8",
     "clip_image_preprocess", "visimage_geometry", "draw_boxes",
     "nf4_quantize", "nf4_dequantize", "nf4_decode_linear", "sample_token",
+    "decode_linear_wide", "wide_prefers_tiles",
 ]
 
 _DT = {torch.bfloat16: DT_BF16, torch.float32: DT_F32}
@@ -476,6 +477,64 @@ def decode_linear(x, w, *, transform: int = 0, norm_w=None, eps: float = 0.0, re
         call("decode_linear_lora", *args, *_decode_lora_args("decode_linear", lora, x), _stream())
     else:
         call("decode_linear", *args, _stream())
+    return y
+
+
+WIDE_M_MIN, WIDE_M_MAX = 17, 64  # cullavo_decode_linear_wide's rows
+
+# (weight rows, K) -> the M ranges (lo, hi) at which the wide product did NOT beat ops.linear's tiles
+# on the same tensors by more than the spread of the tiles' own runs (tools/wide_decode_bench.py part
+# (a); profiles/r21/wide_decode/). The decode step keeps these on the tiles; every other shape,
+# unmeasured ones included, takes the wide product. Measured at M = 17, 32 (the kernel's two-X-block
+# variant) and 64 (its four-block variant, which every M above 32 runs): wide / tiles time, cold weights.
+WIDE_TILES_FASTER = {
+    (12288, 4096): ((17, 64),),   # 7B q|k|v: 1.28 / 1.41 / 1.89 at M = 17 / 32 / 64
+    (4096, 4096): ((33, 64),),    # 7B o: 0.76 / 0.86 at 17 / 32 (wide), 1.15 at 64
+    (22016, 4096): ((32, 64),),   # 7B gate|up + SwiGLU: 0.89 at 17 (wide), 1.01 / 1.35 at 32 / 64
+    (4096, 11008): ((17, 64),),   # 7B down: 1.04 / 1.27 / 1.88
+    (32064, 4096): ((32, 64),),   # 7B lm_head: 0.94 at 17 (wide), 1.00 (inside the 1 % spread) / 1.18 at 32 / 64
+}
+
+
+def wide_prefers_tiles(rows: int, K: int, M: int) -> bool:
+    """True when a [rows, K] weight at M rows stays on ops.linear's tiles (WIDE_TILES_FASTER)"""
+    return any(lo <= M <= hi for lo, hi in WIDE_TILES_FASTER.get((rows, K), ()))
+
+
+def decode_linear_wide(x, w, *, transform: int = 0, residual=None, addend=None, out=None, out_dtype=None):
+    """Decode rows at 17 <= M <= 64 through cullavo_decode_linear_wide: y = x @ w.T with the LoRA term
+    `addend` and `residual` added as ops.linear adds them, bf16(bf16(bf16(acc) + addend) + residual);
+    transform 3: y = SwiGLU(x @ w.T) for the fused gate|up weight w [2N, K] (y [M, N]; no addend, no
+    residual), bitwise swiglu_fwd of the transform-0 product. addend may be a lora.LoraTerm, which is
+    materialised. out: a [M, N] view to write instead of a fresh tensor; out_dtype torch.float32: the
+    f32 sums themselves (transform 0). Row b of y does not depend on the other rows of x."""
+    if addend is not None and hasattr(addend, "materialize"):
+        addend = addend.materialize()
+    _dev(x, w, residual, addend)
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1]:
+        raise ValueError(f"decode_linear_wide: x {tuple(x.shape)} vs w {tuple(w.shape)}")
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise TypeError(f"decode_linear_wide: bf16 rows and weights only, got {x.dtype}, {w.dtype}")
+    M = x.shape[0]
+    N, K = w.shape
+    if transform == 3:
+        N //= 2
+    odt = out.dtype if out is not None and out_dtype is None else (out_dtype or torch.bfloat16)
+    if odt not in _DT:
+        raise TypeError(f"decode_linear_wide: out_dtype {odt} (bf16 / f32 only)")
+    for name, t in (("residual", residual), ("addend", addend)):
+        if t is not None and (t.dtype != torch.bfloat16 or tuple(t.shape) != (M, N)):
+            raise ValueError(f"decode_linear_wide: {name} must be bf16 [{M}, {N}], got {t.dtype} {tuple(t.shape)}")
+    if out is None:
+        y = torch.empty((M, N), dtype=odt, device=x.device)
+    else:
+        _dev(out)
+        if out.dtype != odt or tuple(out.shape) != (M, N):
+            raise ValueError(f"decode_linear_wide: out must be {odt} [{M}, {N}], got {out.dtype} {tuple(out.shape)}")
+        y = out
+    call("decode_linear_wide", int(transform), M, N, K, _ptr(x), _ld(x), _ptr(w), _ld(w), _ptr(y), _ld(y), _DT[odt],
+         _ptr(addend), _ld(addend) if addend is not None else 0, _ptr(residual),
+         _ld(residual) if residual is not None else 0, _stream())
     return y
 
 

@@ -67,7 +67,8 @@ extern "C" {
    cullavo_decode_linear_lora and cullavo_nf4_decode_linear_lora (the decode products with the LoRA
    up-projection in their epilogue), and the FP8 KV cache's six entry points (cullavo_kv_append_fp8,
    cullavo_kv_append_ragged_fp8, cullavo_rope_kv_append_fp8, cullavo_attn_decode_fp8,
-   cullavo_attn_decode_rope_fp8, cullavo_kv_dequant_fp8). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
+   cullavo_attn_decode_rope_fp8, cullavo_kv_dequant_fp8), and cullavo_decode_linear_wide (the decode
+   products at 17 .. 64 rows). A consumer built against this header checks cullavo_abi_version() == CULLAVO_ABI_VERSION at load. */
 #define CULLAVO_ABI_VERSION 9
 
 int cullavo_abi_version(void);
@@ -495,6 +496,23 @@ int cullavo_decode_linear_lora(int x_transform, int64_t M, int64_t N, int64_t K,
                                const void* norm_w, float eps, const void* W, int64_t ldw, void* y, int64_t ldy,
                                const void* residual, int64_t ldr, const void* lora_u, int64_t ld_lora_u,
                                const void* lora_b, int64_t lora_out, int lora_r, float lora_scale, void* stream);
+/* The decode-step Linear at 17 <= M <= 64 rows (added under ABI 9, additive; csrc/gemv_wide.hip): one
+ * token per sequence at batch 17 .. 64, the weight read once at the stream's rate instead of through
+ * the training tiles. x [M, K] bf16 (ldx), W [N, K] bf16 (ldw), y [M, N] (ldy) of y_dtype
+ * (CULLAVO_DT_BF16, or CULLAVO_DT_F32: the f32 sums, for accuracy checks), and
+ *   x_transform 0: y = bf16(bf16(bf16(x W^T) + addend) + residual), addend [M, N] bf16 (ld_addend) and
+ *      residual [M, N] bf16 (ldr) each NULL or given: cullavo_gemm_ex's chain for the two terms;
+ *   x_transform 3: W holds the fused gate|up weight [2N, K] and y [M, N] = SwiGLU(x W^T) as
+ *      cullavo_decode_linear's transform 3 (bf16 only, no addend, no residual).
+ * Transforms 1, 2 and 4 are cullavo_decode_linear's alone (their LDS-staged rows do not fit here).
+ * The sum over K runs in an order fixed by K alone and uses no atomics: row b of y is bitwise the same
+ * whatever other rows the call has. Rows >= M and columns >= N of y are never written.
+ * N, K, ldx, ldw, ldy, ldr % 8 == 0, ld_addend % 4 == 0, leading dimensions >= their row, every pointer
+ * 16-byte aligned, 17 <= M <= 64; anything else: CULLAVO_EINVAL before any launch. */
+int cullavo_decode_linear_wide(int x_transform, int64_t M, int64_t N, int64_t K, const void* x, int64_t ldx,
+                               const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype,
+                               const void* addend, int64_t ld_addend, const void* residual, int64_t ldr,
+                               void* stream);
 /* ---- NF4 base weights (ABI 5) ----------------------------------------------------------------
  * The reference's LM never runs on bf16 base weights: every decoder-layer Linear is bitsandbytes
  * NF4 with bf16 compute, lm_head and the projector skipped (cullavo/load_cullavo.py:66-83). The
